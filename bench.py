@@ -20,8 +20,14 @@ N > 1:  one rank per GPU over RCCL.  `python bench.py --gpus N` with no WORLD_SI
         headline and `config.collective` says so with the reason — never silently.
 
 Frames in flight: `value` / `ms_per_step` are ALWAYS one frame in flight (F = 1), at every N.  `pipelined` re-times the same K
-frames with F = max(3, N) frames in flight (throughput only, labelled).  GPU_MAX_HW_QUEUES=16 is set before HIP starts
-(contexts on separate streams need hardware queues of their own).
+frames with F = max(3, N) frames in flight (throughput only, labelled).  How many hardware queues a process may open is the
+host's setting (contexts on separate streams overlap only as far as they get hardware queues of their own).
+
+`--dump-outputs DIR`: after the timed frames, what the timed path returned in its last step is written as float32 .npy files —
+pathTrace: DIR/direct.npy and DIR/indirect.npy (the whole frame, (W*H, 3), as a caller of rdh_path_trace / rdh_path_trace_gathered
+receives it); restir: DIR/image.npy.  Outputs above 64 MB in all are cut to a fixed, seeded sample of pixels (rows), the same
+from run to run.  The inputs are procedural and the Sobol rows fixed, so two builds run with the same arguments can be compared
+output for output.
 
 value = (closest-hit + any-hit rays actually traced in the K timed frames, all ranks) / (max-over-ranks wall time).
 Ray counts are exact device counters taken in an untimed pass over the same Sobol rows.
@@ -89,7 +95,34 @@ def parse_args():
     ap.add_argument("--frames-in-flight", type=int, default=int(os.environ.get("RADISH_FRAMES_IN_FLIGHT", "1")),
                     help="frames in flight of the HEADLINE measurement (default 1 at every N)")
     ap.add_argument("--master-port", type=int, default=int(os.environ.get("RADISH_MASTER_PORT", "29533")))
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 20261015
+
+
+def dump_outputs(dirpath, arrays):
+    """Write each array of `arrays` (name -> (rows, ...) numpy array) as dirpath/<name>.npy in float32.  If they hold more than
+    DUMP_BUDGET_BYTES in all, every array keeps the same fixed, seeded, sorted sample of rows (pixels) so that the total fits."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, a.shape[0] * DUMP_BUDGET_BYTES // total)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).permutation(a.shape[0])[:keep])
+            a = a[rows]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -298,7 +331,6 @@ def sub_restir(torch, np, api, dev, W, H, K, num_spatial=5):
 # ---------------------------------------------------------------------------------------------------------------------------
 def main():
     args = parse_args()
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # before the HIP runtime starts (children of self_launch inherit it)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
 
@@ -503,6 +535,10 @@ def main():
 
     F = max(1, args.frames_in_flight)
     m = measure(F, lib_comm=(F == 1))
+    if args.dump_outputs and rank == 0:  # the last timed frame, before anything below renders into the same buffers again
+        last = m["slots"][(Wm + K - 1) % F]
+        dump_outputs(args.dump_outputs, {"direct": (last.direct if world == 1 else last.frame_d).cpu().numpy(),
+                                         "indirect": (last.indirect if world == 1 else last.frame_i).cpu().numpy()})
     lib_headline = world > 1 and all(sl.lib_comm for sl in m["slots"])
     cross = None
     if lib_headline:  # the same frames through torch.distributed's collectives, on the same contexts: a cross-check of the headline
@@ -857,6 +893,8 @@ def run_restir(args, torch, np, api, dist, dev, world, rank, backend, barrier, a
         frame(f)
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": frame_img.cpu().numpy()})
     rays_local = float(c["closestRays"] + c["anyRays"])
     if multi:
         st = torch.tensor([el, rays_local], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
