@@ -158,6 +158,28 @@ int rdh_synchronize(rdh_ctx *ctx);
 /* Replaces DevScene::create (src/scene.cpp:461-551): uploads and re-lays-out the scene (32-byte threaded nodes,
  * 48-byte triangle records, packed light records).  Blocking. */
 int rdh_scene_upload(rdh_ctx *ctx, const rdh_scene_desc *desc);
+/* ---- moving geometry (no reference counterpart: the reference rebuilds and re-uploads the whole scene) ------------------------
+ * rdh_build_bvh_device: the device twin of rdh_build_bvh (include/radish_host.h) — d_vertices float[3*numPrims][3] -> d_boxes
+ * float[2*numPrims-1][6] and d_nodes[k] int32[2*numPrims-1][3] = {primitiveId, boundingBoxId, nextNodeIfMiss}, bit for bit what the
+ * host builder writes.  Device pointers; asynchronous on the context's stream; needs no scene.
+ * rdh_scene_update_geometry: new positions for the SAME triangles of the uploaded scene (same count, materials, texcoords, light
+ * list): d_vertices float[3*numPrims][3] (device), d_normals likewise or NULL (keep the uploaded normals), lights NULL (keep the
+ * light table and sumLightPowerInv) or the moved lights' table.  Rewrites the triangle records, builds the tree on the device (the
+ * tree rdh_build_bvh makes of these vertices), its six threaded arrays, sibling pairs and root box, the emissive triangles' records
+ * and their per-light constants.  Asynchronous on the context's stream (the next render call waits for the build before it
+ * launches); restarts the persistent block order; ReSTIR reservoirs are kept.  Coordinates must be finite and below 1e30, as for
+ * rdh_scene_upload (not checked here: that would need the vertices on the host). */
+typedef struct rdh_light_update {
+    const void *lightSampler;   /* HOST BinomialDistrib<float>[lightSamplerLength], as in rdh_scene_desc              */
+    int32_t lightSamplerLength; /* must equal the uploaded scene's                                                   */
+    float sumLightPowerInv;
+} rdh_light_update;
+int rdh_build_bvh_device(rdh_ctx *ctx, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]);
+int rdh_scene_update_geometry(rdh_ctx *ctx, const float *d_vertices, const float *d_normals, const rdh_light_update *lights);
+/* Test access to the tree the kernels walk: which = 0 the six NodeRec arrays (6 x (bvhSize + 1) x 32 B, pad records included),
+ * 1 the sibling pairs ((bvhSize - 1) / 2 + 1 records of 64 B; 0 bytes when the scene has none), 2 {int32 treeDepth, hasPairs, 0, 0;
+ * float rootLo[4]; float rootHi[4]} (48 B).  Returns the byte size (hostOut NULL: only that) or a negative RDH_ERR_*.  Blocking. */
+long long rdh_debug_read_tree(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
 /* Replaces DevScene::destroy (src/scene.cpp:553-574). */
 int rdh_scene_free(rdh_ctx *ctx);
 /* The `Camera cam` kernel argument of every reference kernel (State::scene->camera, src/pathtrace.cu:356). */

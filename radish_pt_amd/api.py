@@ -55,6 +55,7 @@ EXPORTS = [
     "rdh_dump_rays", "rdh_set_occupancy_share", "rdh_allgather_tiles", "rdh_path_trace_gathered", "rdh_restir_exchange", "rdh_restir_direct_gathered", "rdh_gbuffer_exchange",
     "rdh_comm_init_all", "rdh_path_trace_gathered_all", "rdh_gbuffer_exchange_all", "rdh_restir_direct_gathered_all",
     "rdh_comm_set_overlap", "rdh_comm_join",
+    "rdh_build_bvh_device", "rdh_scene_update_geometry", "rdh_debug_read_tree",
 ]
 
 
@@ -69,6 +70,10 @@ class SceneDescC(C.Structure):
         ("numTextures", C.c_int32), ("textures", C.c_void_p), ("envMapTexId", C.c_int32),
         ("envMapSamplerLength", C.c_int32), ("envMapSampler", C.c_void_p),
     ]
+
+
+class LightUpdateC(C.Structure):  # rdh_light_update
+    _fields_ = [("lightSampler", C.c_void_p), ("lightSamplerLength", C.c_int32), ("sumLightPowerInv", C.c_float)]
 
 
 class TextureC(C.Structure):  # rdh_texture
@@ -168,6 +173,9 @@ def lib():
             "rdh_gbuffer_exchange": ([vp, C.POINTER(GBufferC)], i32),
             "rdh_dump_rays": ([vp, i32, i32, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)], i32),
             "rdh_set_occupancy_share": ([vp, i32], i32),
+            "rdh_build_bvh_device": ([vp, vp, i32, vp, C.POINTER(vp)], i32),
+            "rdh_scene_update_geometry": ([vp, vp, vp, C.POINTER(LightUpdateC)], i32),
+            "rdh_debug_read_tree": ([vp, i32, vp, i64], i64),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -269,6 +277,56 @@ class Context:
         d.envMapSamplerLength = 0 if env is None else len(env)
         d.envMapSampler = None if env is None or len(env) == 0 else env.ctypes.data
         self.check(lib().rdh_scene_upload(self.h, C.byref(d)))
+        self._num_prims = int(sd.num_prims)
+
+    # ---- moving geometry: the device BVH builder ----
+    def build_bvh_device(self, vertices):
+        """vertices: float32 cuda tensor [3N, 3] (or [N, 3, 3]) -> (boxes float32 [2N-1, 6], nodes int32 [6, 2N-1, 3]) on the device,
+        bit for bit hostlib.build_bvh of the same soup.  Asynchronous on the context's stream."""
+        torch = _torch()
+        if not isinstance(vertices, torch.Tensor) or vertices.numel() == 0 or vertices.numel() % 9:
+            raise RadishError("build_bvh_device: vertices must be a tensor of 9*N floats (N >= 1)")
+        n = vertices.numel() // 9
+        vp = self._ptr(vertices, 9 * n, "build_bvh_device vertices")
+        size = 2 * n - 1
+        boxes = torch.empty(size, 6, dtype=torch.float32, device=vertices.device)
+        nodes = torch.empty(6, size, 3, dtype=torch.int32, device=vertices.device)
+        ptrs = (C.c_void_p * 6)(*[nodes[k].data_ptr() for k in range(6)])
+        self.check(lib().rdh_build_bvh_device(self.h, vp, n, boxes.data_ptr(), ptrs))
+        return boxes, nodes
+
+    def update_geometry(self, vertices, normals=None, lights=None):
+        """New positions for the uploaded scene's triangles (same count and order): vertices / normals float32 cuda tensors of
+        9*numPrims floats; lights None (keep the light table) or (light_sampler, sum_light_power_inv) with light_sampler a
+        layouts.BINOMIAL_DTYPE array of the scene's length.  Rebuilds the tree on the device; does not block."""
+        n = getattr(self, "_num_prims", None)
+        if n is None:
+            raise RadishError("update_geometry: no scene uploaded")
+        torch = _torch()
+        for t, what in ((vertices, "vertices"), (normals, "normals")):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.numel() != 9 * n):
+                got = t.numel() if isinstance(t, torch.Tensor) else type(t).__name__
+                raise RadishError(f"update_geometry: {what} must hold 9*{n} floats (the uploaded triangle count), got {got}")
+        vp = self._ptr(vertices, 9 * n, "update_geometry vertices")
+        np_ = None if normals is None else self._ptr(normals, 9 * n, "update_geometry normals")
+        lu = None
+        if lights is not None:
+            table, inv = lights
+            table = np.ascontiguousarray(table, dtype=L.BINOMIAL_DTYPE)
+            lu = LightUpdateC(table.ctypes.data if len(table) else None, len(table), float(inv))
+        self.check(lib().rdh_scene_update_geometry(self.h, vp, np_, None if lu is None else C.byref(lu)))
+
+    def debug_read_tree(self, which):
+        """Blocking test access (rdh_debug_read_tree): 0 -> NodeRec bytes, 1 -> PairRec bytes, 2 -> the 48-byte header."""
+        n = lib().rdh_debug_read_tree(self.h, which, None, 0)
+        if n < 0:
+            self.check(int(n))
+        out = np.zeros(n, np.uint8)
+        if n:
+            rc = lib().rdh_debug_read_tree(self.h, which, out.ctypes.data, n)
+            if rc < 0:
+                self.check(int(rc))
+        return out
 
     def set_camera(self, cam):
         buf = np.frombuffer(np.asarray(cam, dtype=L.CAMERA_DTYPE).tobytes(), np.uint8).copy()

@@ -24,6 +24,7 @@
 #include "device/kernels_walk.h"
 #include "device/kernels_display.h"
 #include "device/kernels_denoise.h"
+#include "device/kernels_bvh.h"
 
 using namespace rd;
 
@@ -122,6 +123,24 @@ struct rdh_ctx {
     long long wfCapacity = 0;   // path slots each workspace holds
     std::vector<void *> wfAllocs;
     hipEvent_t evWfFork = nullptr, evWfJoin = nullptr;
+
+    // device BVH builder (kernels_bvh.h) and rdh_scene_update_geometry
+    void *bvhScratch = nullptr;      // BvhWork buffers for bvhCap primitives, one allocation
+    int bvhCap = 0;
+    void *updTree = nullptr;         // the update's boxes + six int[S][3] orderings, for updCap primitives
+    int updCap = 0;
+    int *dLightPrims = nullptr;      // the uploaded scene's lightPrimIds (scene allocation)
+    int numLights = 0;
+    PairRec *updPairs = nullptr;     // pairs of an updated tree when the upload had none (scene allocation)
+    int4 *dTreeHdr = nullptr;        // k_bvh_pairs' header: {treeDepth, error}, rootLo, rootHi
+    int4 *hTreeHdr = nullptr;        // its pinned host copy
+    hipEvent_t evTree = nullptr;     // recorded after that copy
+    bool treePending = false;        // an update's header has not been folded into ds yet (settleTree)
+    AliasRec *hAliasStage[2] = {nullptr, nullptr};  // pinned staging of the light tables of the last two updates
+    int aliasStageCap[2] = {0, 0};
+    hipEvent_t evAliasStage[2] = {nullptr, nullptr};
+    int aliasStageNext = 0;
+    hipEvent_t evUpdWait = nullptr;
 };
 
 namespace {
@@ -338,8 +357,39 @@ unsigned gridFor(const PixelMap &pm) {
 
 unsigned gridBlocks(const PixelMap &pm) { return (((unsigned)pm.numBlocks + 7u) / 8u) * 8u; }  // single-wave workgroups
 
+// Fold the tree header of the last rdh_scene_update_geometry into ds (the kernels take treeDepth, the root box and whether pairs
+// exist as launch arguments): waits for that update's build, which the stream has to finish before the next launch anyway.
+int settleTree(rdh_ctx *c) {
+    if (!c->treePending) return RDH_OK;
+    HIP_TRY(c, hipEventSynchronize(c->evTree));
+    c->treePending = false;
+    const int4 h0 = c->hTreeHdr[0], lo = c->hTreeHdr[1], hi = c->hTreeHdr[2];
+    if (h0.y != 0) {
+        c->haveScene = false;
+        return fail(c, RDH_ERR_STATE, "device BVH build failed (error bits %d); the scene must be uploaded again", h0.y);
+    }
+    constexpr int kMaxPairDepth = 2048;  // as rdh_scene_upload
+    const PairRec *pairs = c->updPairs ? c->updPairs : c->ds.pairs;
+    if (h0.x <= kMaxPairDepth) {
+        c->ds.pairs = pairs;
+        c->ds.treeDepth = h0.x;
+        c->ds.rootLo = make_float4(__builtin_bit_cast(float, lo.x), __builtin_bit_cast(float, lo.y), __builtin_bit_cast(float, lo.z),
+                                   __builtin_bit_cast(float, lo.w));
+        c->ds.rootHi = make_float4(__builtin_bit_cast(float, hi.x), __builtin_bit_cast(float, hi.y), __builtin_bit_cast(float, hi.z),
+                                   __builtin_bit_cast(float, hi.w));
+    } else {
+        c->ds.pairs = nullptr;
+        c->ds.treeDepth = 0;
+    }
+    return RDH_OK;
+}
+
 int requireReady(rdh_ctx *c) {
     if (!c) return RDH_ERR_ARGS;
+    if (c->haveScene) {
+        int rc = settleTree(c);
+        if (rc) return rc;
+    }
     if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded (rdh_scene_upload)");
     if (!c->haveCamera) return fail(c, RDH_ERR_NO_SCENE, "no camera set (rdh_set_camera)");
     return RDH_OK;
@@ -683,6 +733,10 @@ int rdh_scene_free(rdh_ctx *c) {
     for (void *p : c->sceneAllocs) hipFree(p);
     c->sceneAllocs.clear();
     c->haveScene = false;
+    c->treePending = false;
+    c->dLightPrims = nullptr;
+    c->updPairs = nullptr;
+    c->numLights = 0;
     return RDH_OK;
 }
 
@@ -700,6 +754,16 @@ void rdh_destroy(rdh_ctx *c) {
     if (c->treeOvf) hipFree(c->treeOvf);
     for (int h = 0; h < 3; h++)
         if (c->wfTreeOvf[h]) hipFree(c->wfTreeOvf[h]);
+    if (c->bvhScratch) hipFree(c->bvhScratch);
+    if (c->updTree) hipFree(c->updTree);
+    if (c->dTreeHdr) hipFree(c->dTreeHdr);
+    if (c->hTreeHdr) hipHostFree(c->hTreeHdr);
+    if (c->evTree) hipEventDestroy(c->evTree);
+    if (c->evUpdWait) hipEventDestroy(c->evUpdWait);
+    for (int k = 0; k < 2; k++) {
+        if (c->hAliasStage[k]) hipHostFree(c->hAliasStage[k]);
+        if (c->evAliasStage[k]) hipEventDestroy(c->evAliasStage[k]);
+    }
     if (c->sideStream) hipStreamSynchronize(c->sideStream);
     if (c->litStream && c->litStream != c->sideStream) {
         hipStreamSynchronize(c->litStream);
@@ -907,6 +971,13 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
         lights[i].c = make_float4(v[8], r[0], r[1], r[2]);
     }
     if ((rc = uploadVec(c, lights, &c->ds.lights))) return rc;
+    {  // kept for rdh_scene_update_geometry, which rebuilds the LightRecs from moved vertices
+        std::vector<int> lp(d->lightPrimIds, d->lightPrimIds + d->numLights);
+        const int *dp = nullptr;
+        if ((rc = uploadVec(c, lp, &dp))) return rc;
+        c->dLightPrims = const_cast<int *>(dp);
+        c->numLights = d->numLights;
+    }
     {  // per-light constants of the RIS loop, computed on the device with the functions the per-candidate code uses
         void *pre = nullptr;
         HIP_TRY(c, hipMalloc(&pre, std::max<size_t>(sizeof(LightPre) * lights.size(), 64)));
@@ -1999,6 +2070,7 @@ static int walkPersistent(rdh_ctx *c, const float *d_rays, int64_t n, int4 *d_hi
 int rdh_trace_closest(rdh_ctx *c, const float *d_rays, int64_t n, rdh_hit *d_hits, uint32_t flags) {
     if (!c) return RDH_ERR_ARGS;
     if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (int rc = settleTree(c)) return rc;
     if (n < 0 || (n > 0 && (!d_rays || !d_hits))) return fail(c, RDH_ERR_ARGS, "rdh_trace_closest: bad arguments");
     if (n == 0) return RDH_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2015,6 +2087,7 @@ int rdh_trace_closest(rdh_ctx *c, const float *d_rays, int64_t n, rdh_hit *d_hit
 int rdh_trace_occluded(rdh_ctx *c, const float *d_seg, int64_t n, int32_t *d_occ, uint32_t flags) {
     if (!c) return RDH_ERR_ARGS;
     if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (int rc = settleTree(c)) return rc;
     if (n < 0 || (n > 0 && (!d_seg || !d_occ))) return fail(c, RDH_ERR_ARGS, "rdh_trace_occluded: bad arguments");
     if (n == 0) return RDH_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2292,6 +2365,192 @@ int rdh_last_kernel_ms(rdh_ctx *c, float *ms) {
     HIP_TRY(c, hipEventSynchronize(c->evStop));
     HIP_TRY(c, hipEventElapsedTime(ms, c->evStart, c->evStop));
     return RDH_OK;
+}
+
+}  // extern "C"
+
+// ---- device BVH builder (kernels_bvh.h) -------------------------------------------------------------------------------------------
+namespace {
+
+size_t alignUp(size_t x) { return (x + 255) & ~size_t(255); }
+
+// Workspace of k_bvh_build for N primitives (grown on demand, kept by the context); outputs are filled in by the caller.
+int bvhWorkspace(rdh_ctx *c, int N, BvhWork &w) {
+    const size_t S = 2 * (size_t)N - 1, jobs = std::max(N - 1, 1);
+    const size_t prims = alignUp(sizeof(BvhPrim) * (size_t)N), queue = alignUp(sizeof(BvhJob) * jobs), slots = alignUp(sizeof(int) * S);
+    if (N > c->bvhCap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->bvhScratch) hipFree(c->bvhScratch);
+        c->bvhScratch = nullptr;
+        c->bvhCap = 0;
+        HIP_TRY(c, hipMalloc(&c->bvhScratch, 2 * prims + queue + 3 * slots + 256));
+        c->bvhCap = N;
+    }
+    char *p = static_cast<char *>(c->bvhScratch);
+    w.prims[0] = reinterpret_cast<BvhPrim *>(p);
+    w.prims[1] = reinterpret_cast<BvhPrim *>(p + prims);
+    w.queue = reinterpret_cast<BvhJob *>(p + 2 * prims);
+    w.info = reinterpret_cast<int *>(p + 2 * prims + queue);
+    w.bits = reinterpret_cast<int *>(p + 2 * prims + queue + slots);
+    w.qnum = reinterpret_cast<int *>(p + 2 * prims + queue + 2 * slots);
+    w.ctl = reinterpret_cast<int *>(p + 2 * prims + queue + 3 * slots);
+    w.numPrims = N;
+    return RDH_OK;
+}
+
+// Builds the tree of w.verts into w.boxes / w.nodes on the context's stream (no host synchronisation).
+int launchBvhBuild(rdh_ctx *c, BvhWork &w) {
+    const int N = w.numPrims, jobs = std::max(N - 1, 1);
+    hipLaunchKernelGGL(k_bvh_clear_queue, dim3((unsigned)((jobs + 255) / 256)), dim3(256), 0, c->stream, w.queue, jobs, 0);
+    hipLaunchKernelGGL(k_bvh_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, w);
+    if (N > 1) {
+        // as many workgroups as can make progress at once: the queue never holds more than N - 1 jobs
+        int cus = 0;
+        HIP_TRY(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        const unsigned grid = (unsigned)std::min<long long>((long long)std::max(cus, 1) * 4, N - 1);
+        hipLaunchKernelGGL(k_bvh_build, dim3(grid), dim3(kBvhThreads), 0, c->stream, w);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return RDH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_build_bvh_device(rdh_ctx *c, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: bad arguments");
+    for (int k = 0; k < 6; k++)
+        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: d_nodes[%d] is null", k);
+    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: %d primitives", numPrims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    BvhWork w{};
+    int rc = bvhWorkspace(c, numPrims, w);
+    if (rc) return rc;
+    w.verts = d_vertices;
+    w.boxes = d_boxes;
+    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
+    return launchBvhBuild(c, w);
+}
+
+int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: no scene uploaded");
+    if (!d_vertices) return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: d_vertices is null");
+    if (lights) {
+        if (lights->lightSamplerLength != c->ds.lightSamplerLength)
+            return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: lightSamplerLength %d != the scene's %d", lights->lightSamplerLength,
+                        c->ds.lightSamplerLength);
+        if (lights->lightSamplerLength > 0 && !lights->lightSampler)
+            return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: lightSampler is null");
+        const AliasRec *a = static_cast<const AliasRec *>(lights->lightSampler);
+        for (int i = 0; i < lights->lightSamplerLength; i++)
+            if (a[i].failId < 0 || a[i].failId >= lights->lightSamplerLength)
+                return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: alias table failId out of range");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    if (!c->evTree) {
+        HIP_TRY(c, hipEventCreateWithFlags(&c->evTree, hipEventDisableTiming));
+        HIP_TRY(c, hipEventCreateWithFlags(&c->evUpdWait, hipEventDisableTiming));
+        for (int k = 0; k < 2; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->evAliasStage[k], hipEventDisableTiming));
+        HIP_TRY(c, hipMalloc((void **)&c->dTreeHdr, 3 * sizeof(int4)));
+        HIP_TRY(c, hipHostMalloc((void **)&c->hTreeHdr, 3 * sizeof(int4), hipHostMallocDefault));
+    }
+    // The scene's arrays are rewritten in place: launches still in flight on the side streams read them, so wait for those
+    for (hipStream_t side : {c->sideStream, c->litStream, c->wfStream}) {
+        if (!side || side == c->stream) continue;
+        HIP_TRY(c, hipEventRecord(c->evUpdWait, side));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evUpdWait, 0));
+    }
+    if (!c->ds.pairs && !c->updPairs) {  // the upload had no pairs; an updated tree always has them
+        void *p = nullptr;
+        HIP_TRY(c, hipMalloc(&p, sizeof(PairRec) * ((size_t)(S - 1) / 2 + 1)));
+        c->sceneAllocs.push_back(p);
+        c->updPairs = static_cast<PairRec *>(p);
+    }
+    PairRec *pairs = c->updPairs ? c->updPairs : const_cast<PairRec *>(c->ds.pairs);
+    if (N > c->updCap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->updTree) hipFree(c->updTree);
+        c->updTree = nullptr;
+        c->updCap = 0;
+        HIP_TRY(c, hipMalloc(&c->updTree, alignUp(sizeof(float) * 6 * (size_t)S) + 6 * alignUp(sizeof(int) * 3 * (size_t)S)));
+        c->updCap = N;
+    }
+    BvhWork w{};
+    int rc = bvhWorkspace(c, N, w);
+    if (rc) return rc;
+    char *t = static_cast<char *>(c->updTree);
+    w.verts = d_vertices;
+    w.boxes = reinterpret_cast<float *>(t);
+    for (int k = 0; k < 6; k++)
+        w.nodes[k] = reinterpret_cast<int *>(t + alignUp(sizeof(float) * 6 * (size_t)S) + k * alignUp(sizeof(int) * 3 * (size_t)S));
+
+    // triangles, attributes, emissive triangles
+    const int geomN = std::max(N, c->numLights);
+    hipLaunchKernelGGL(k_geom_update, dim3((unsigned)((geomN + 255) / 256)), dim3(256), 0, c->stream, d_vertices, d_normals,
+                       const_cast<TriRec *>(c->ds.tris), const_cast<AttrRec *>(c->ds.attrs), N, const_cast<LightRec *>(c->ds.lights),
+                       (const int *)c->dLightPrims, c->numLights);
+    if (lights && lights->lightSamplerLength > 0) {  // the caller's table goes through a pinned staging buffer: no host wait
+        const int s = c->aliasStageNext, len = lights->lightSamplerLength;
+        c->aliasStageNext ^= 1;
+        HIP_TRY(c, hipEventSynchronize(c->evAliasStage[s]));  // the copy of two updates ago (long done, normally)
+        if (c->aliasStageCap[s] < len) {
+            if (c->hAliasStage[s]) hipHostFree(c->hAliasStage[s]);
+            c->hAliasStage[s] = nullptr;
+            c->aliasStageCap[s] = 0;
+            HIP_TRY(c, hipHostMalloc((void **)&c->hAliasStage[s], sizeof(AliasRec) * len, hipHostMallocDefault));
+            c->aliasStageCap[s] = len;
+        }
+        memcpy(c->hAliasStage[s], lights->lightSampler, sizeof(AliasRec) * len);
+        HIP_TRY(c, hipMemcpyAsync(const_cast<AliasRec *>(c->ds.lightAlias), c->hAliasStage[s], sizeof(AliasRec) * len, hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipEventRecord(c->evAliasStage[s], c->stream));
+    }
+    if (lights) c->ds.sumLightPowerInv = lights->sumLightPowerInv;
+    if (c->numLights > 0)
+        hipLaunchKernelGGL(k_light_precompute, dim3((unsigned)((c->numLights + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights,
+                           const_cast<LightPre *>(c->ds.lightPre), c->numLights, c->ds.sumLightPowerInv);
+
+    // the tree and what the upload derives from it
+    if ((rc = launchBvhBuild(c, w))) return rc;
+    const long long recs = 6ll * (S + 1);
+    hipLaunchKernelGGL(k_bvh_noderecs, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, c->stream, (const float *)w.boxes, w,
+                       const_cast<NodeRec *>(c->ds.nodes[0]), S);
+    hipLaunchKernelGGL(k_bvh_pairs, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, w, pairs, c->dTreeHdr);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr, c->dTreeHdr, 3 * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evTree, c->stream));
+    c->treePending = true;
+    c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
+    return RDH_OK;
+}
+
+long long rdh_debug_read_tree(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (int rc = settleTree(c)) return rc;
+    const int S = c->ds.bvhSize;
+    long long bytes;
+    if (which == 0) bytes = (long long)sizeof(NodeRec) * 6 * (S + 1);
+    else if (which == 1) bytes = c->ds.pairs ? (long long)sizeof(PairRec) * ((S - 1) / 2 + 1) : 0;
+    else if (which == 2) bytes = 48;
+    else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_tree: which = %d", which);
+    if (!hostOut) return bytes;
+    if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_tree: %lld bytes needed", bytes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (which == 0) HIP_TRY(c, hipMemcpy(hostOut, c->ds.nodes[0], bytes, hipMemcpyDeviceToHost));
+    else if (which == 1 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.pairs, bytes, hipMemcpyDeviceToHost));
+    else if (which == 2) {
+        int32_t h[4] = {c->ds.treeDepth, c->ds.pairs ? 1 : 0, 0, 0};
+        memcpy(hostOut, h, 16);
+        memcpy(static_cast<char *>(hostOut) + 16, &c->ds.rootLo, 16);
+        memcpy(static_cast<char *>(hostOut) + 32, &c->ds.rootHi, 16);
+    }
+    return bytes;
 }
 
 }  // extern "C"
