@@ -32,12 +32,18 @@ struct alignas(128) WaveCounter {
     int v;
     int pad[31];
 };
+#ifndef RD_WF_TICKET_SHARDS
+#define RD_WF_TICKET_SHARDS 8  // workgroup-ticket counters per stage (workgroupTicket); 1: one chip-wide counter (measurements)
+#endif
+constexpr int kTicketShards = RD_WF_TICKET_SHARDS;
 struct WaveCounters {
     WaveCounter rayCount[kMaxWaveDepth + 2];     // rays of bounce k (written by raygen / shade(k-1))
     WaveCounter shadowCount[kMaxWaveDepth + 2];  // shadow rays emitted by shade(k)
     WaveCounter litCount[kMaxWaveDepth + 2];     // literal-class rays (both kinds) that shade(k-1) set aside for trace(k)
     WaveCounter traceHead[kMaxWaveDepth + 2];
     WaveCounter shadeHead[kMaxWaveDepth + 2][4];
+    WaveCounter traceTicket[kMaxWaveDepth + 2][kTicketShards];  // workgroupTicket of trace(k) / shade(k)
+    WaveCounter shadeTicket[kMaxWaveDepth + 2][kTicketShards];
 };
 
 struct WaveWorkspace {
@@ -55,7 +61,7 @@ struct WaveWorkspace {
     int *shadowq;
     int *litq[2];     // path slots of rays that look literal-class (bit 30: a shadow ray); trace(k) starts them first, one per wave
     int litCap;       // entries a stage may hold: min(kWfLitCap, 64 * waves of the trace grid)
-    int *treeOvf;     // k_wf_trace<.., true>: its lanes' stacks beyond their LDS rings, [wave of the grid][treeOvfDepth][64] int2 (traverse.h, pairPush)
+    int *treeOvf;     // k_wf_trace<.., true>: its lanes' stacks beyond their LDS rings, [logical wave][treeOvfDepth][64] int2 (traverse.h, pairPush)
     int treeOvfDepth;
     WaveCounters *ctr;
 };
@@ -96,12 +102,31 @@ RD_DEV void waveAppendN(const bool (&pred)[kShadeChunks], const int (&item)[kSha
 }
 
 // Work distribution for the persistent kernels.  Same-address returning atomics serialise chip-wide at ~12 ns each
-// (MI355X_MICROARCH.md "dequeue"/"fanin"), so (a) every wave's FIRST packet is static — wave g takes items
-// [g*kPacket, (g+1)*kPacket) — and the shared head only hands out what lies beyond gridWaves*kPacket, and (b) a pull
-// reserves kPacket = 128 items.  Heads are zeroed once per frame by the counters memset.
+// (MI355X_MICROARCH.md "dequeue"/"fanin"), so (a) every wave's FIRST packet is fixed by its LOGICAL wave g — wave g takes
+// items [g*kPacket, (g+1)*kPacket) — and the shared head only hands out what lies beyond gridWaves*kPacket, and (b) a pull
+// reserves kPacket = 128 items.  Heads and tickets are zeroed once per frame by the counters memset.
+//
+// The logical wave comes from the workgroup's ticket, taken in the order the workgroups become resident, not from blockIdx:
+// a launch is not alone on the chip (the sub-frame pipelines each launch the whole resident grid, and two of them may share a
+// hardware queue or run side by side), so the dispatcher may hold some workgroups back until another launch's tail frees
+// their slots.  With blockIdx those late workgroups would start their fixed share — first packets, literal-class list entries —
+// late; with tickets whatever starts late takes what nobody has taken yet.  Cost: one returning atomic per WORKGROUP, spread
+// over kTicketShards = 8 counters (workgroup b uses counter b % 8, the XCD the dispatcher dealt it to), not one per wave.
 constexpr int kPacket = 128;
-RD_DEV int globalWave() { return int(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); }
 RD_DEV int gridWaves() { return int(gridDim.x * (blockDim.x >> 6)); }
+// The workgroup's logical index in [0, gridDim.x), a permutation of blockIdx.x: shard x holds exactly the workgroups
+// b = x + S t < gridDim.x (S = kTicketShards), and its t-th ticket becomes x + S t.  Every thread of the workgroup must call it (barrier).
+RD_DEV int workgroupTicket(WaveCounter *tickets) {
+    __shared__ int ticket;
+    if (threadIdx.x == 0) {
+        const unsigned x = blockIdx.x % (unsigned)kTicketShards;
+        ticket = int(x + (unsigned)kTicketShards * (unsigned)atomicAdd(&tickets[x].v, 1));
+    }
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(ticket);
+}
+// (wave-uniform, so kept in a scalar register: the VGPR budget of k_wf_trace has no room for it)
+RD_DEV int logicalWave(int wg) { return __builtin_amdgcn_readfirstlane(int(wg * int(blockDim.x >> 6) + int(threadIdx.x >> 6))); }
 RD_DEV int wavePull(int *head, int packet = kPacket) {
     int base = 0;
     if ((threadIdx.x & 63u) == 0u) base = atomicAdd(head, packet);
@@ -173,12 +198,16 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
 // children fetched and tested per round trip, the far one re-checked when the walk reaches it; traverse.h, pairStep) instead of the
 // six threaded arrays — same triangle tests in the same order, same counters.  Chosen by the host for big scenes (radish_hip.hip,
 // usePairs): a sixth of the node footprint and half the dependent round trips (profiles/r03_h_*).
+#ifndef RD_WF_TRACE_WAVES  // waves per SIMD the threaded variant is held to: its occupancy step (72 VGPRs).  Unbounded, the entry
+#define RD_WF_TRACE_WAVES 7  // barrier of workgroupTicket makes the allocator take 73 (6 waves); held to 7 it takes 70, no scratch
+#endif
 #ifndef RD_WF_PAIR_WAVES
 #define RD_WF_PAIR_WAVES 1  // waves per SIMD the pair variant is held to (1: whatever its registers allow)
 #endif
 template <bool COUNT, bool PAIRS = false>
-__global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : 1) void k_wf_trace(DScene s, WaveWorkspace w, int k) {
+__global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ? RD_WF_TRACE_WAVES : 1)) void k_wf_trace(DScene s, WaveWorkspace w, int k) {
     WaveCounters *c = w.ctr;
+    const int wg = workgroupTicket(c->traceTicket[k]);  // stands for blockIdx.x below (see wavePull)
     const int nShadow = (k > 0) ? c->shadowCount[k - 1].v : 0;
     const int nRay = c->rayCount[k].v;
     const int total = nShadow + nRay;
@@ -188,8 +217,8 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : 1) void k
     const int end = s.bvhSize;
     const int END = end;  // `node` of a finished walk (!PAIRS)
 
-    // wave-uniform reservation of work items; the first one is static (see wavePull)
-    int resNext = globalWave() * kPacket, resEnd = resNext + kPacket;
+    // wave-uniform reservation of work items; the first one is the logical wave's (see wavePull)
+    int resNext = logicalWave(wg) * kPacket, resEnd = resNext + kPacket;
     bool exhausted = resNext >= total;
     if (resEnd > total) resEnd = total;
 
@@ -213,7 +242,8 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : 1) void k
     // (median) to 1.5 ms for one of them on the teapots scene) start FIRST: picked up with a late packet one of them is what the stage
     // ends on (measured ceiling: 0.5-0.95 ms of the teapots frame).  Round 3: the workgroup traces them TOGETHER — its four waves are
     // at the same point only here, before each goes its own way with lane refill — 256 records per round trip with the parallel
-    // resolve of wg_trace.h instead of 64 with a scalar one (coopTraceWhole): entry `it` of the list belongs to workgroup it % grid.
+    // resolve of wg_trace.h instead of 64 with a scalar one (coopTraceWhole): entry `it` of the list belongs to the workgroup whose
+    // ticket is it % grid, so the workgroups that become resident first take the list.
     // The list is a HINT (shade classifies by the direction it emits, this kernel by the ray it builds): an entry whose ray turns out
     // ordinary is left to a lane of the workgroup (first round below), as before.
     // (PAIRS: the four waves' stack rows take over the workgroup trace's LDS once the list is done)
@@ -224,9 +254,9 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : 1) void k
     } lds;
     WgTraceSharedT<256> &wgsh = lds.wg;
     int2 *const stk = lds.stack + (PAIRS ? int(threadIdx.x >> 6) * kPairLds * 64 : 0);
-    int2 *const ovf = PAIRS ? reinterpret_cast<int2 *>(w.treeOvf) + (size_t)globalWave() * (size_t)w.treeOvfDepth * 64 : nullptr;
+    int2 *const ovf = PAIRS ? reinterpret_cast<int2 *>(w.treeOvf) + (size_t)logicalWave(wg) * (size_t)w.treeOvfDepth * 64 : nullptr;
     const int nLit = c->litCount[k].v < w.litCap ? c->litCount[k].v : w.litCap;
-    for (int it = int(blockIdx.x); it < nLit; it += int(gridDim.x)) {  // uniform over the workgroup
+    for (int it = wg; it < nLit; it += int(gridDim.x)) {  // uniform over the workgroup
         const int e = w.litq[k & 1][it];
         const bool sh = (e & kWfLitShadow) != 0;
         const int pp = e & (kWfLitShadow - 1);
@@ -281,7 +311,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : 1) void k
         if (firstRound) {
             firstRound = false;
             // the workgroup's j-th entry (j = 4 * lane + wave of the workgroup: at most 256 per workgroup) — see above
-            const int it = int(blockIdx.x) + (int(threadIdx.x & 63u) * 4 + int(threadIdx.x >> 6)) * int(gridDim.x);
+            const int it = wg + (int(threadIdx.x & 63u) * 4 + int(threadIdx.x >> 6)) * int(gridDim.x);
             if (it < nLit) {
                 const int e = w.litq[k & 1][it];
                 doStart = true;
@@ -515,6 +545,7 @@ constexpr int kSortPacket = 64 * kSortChunks;    // records a wave bins at a tim
 __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, WaveWorkspace w, int k, int maxDepth, int sorted) {
     __shared__ int sSorted[4][kSortPacket];  // per wave of the workgroup: the packet's path slots in class order
     WaveCounters *c = w.ctr;
+    const int wg = workgroupTicket(c->shadeTicket[k]);  // stands for blockIdx.x (see wavePull)
     const int lane = int(threadIdx.x & 63u);
     int *mySorted = sSorted[threadIdx.x >> 6];
     {
@@ -539,7 +570,7 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
             packet = packet < kShadePacket ? kShadePacket : (packet > kSortPacket ? kSortPacket : packet);
         }
         int packetEnd = 0;  // sorted: records of the current packet that exist (<= kSortPacket)
-        for (int base = globalWave() * packet, sub = 0, fresh = 1;;) {
+        for (int base = logicalWave(wg) * packet, sub = 0, fresh = 1;;) {
             if (sub == packet) {
                 base = wavePull(&c->shadeHead[k][q].v, packet);
                 sub = 0;
