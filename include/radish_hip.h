@@ -177,6 +177,21 @@ typedef struct rdh_light_update {
 } rdh_light_update;
 int rdh_build_bvh_device(rdh_ctx *ctx, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]);
 int rdh_scene_update_geometry(rdh_ctx *ctx, const float *d_vertices, const float *d_normals, const rdh_light_update *lights);
+/* rdh_scene_refit_geometry: the same arguments, checks and light handling as rdh_scene_update_geometry, but the tree KEEPS its
+ * topology: leaf primitives, the emission order and miss links of the six orderings, pair numbering, pair w fields and
+ * ordering bits, and treeDepth all stay; only the boxes are recomputed, bottom-up: a leaf's box is bvhLo / bvhHi folded over its
+ * three vertices in order from the empty box, an inner node's box is combLo / combHi of its two children, ordering 0's first child
+ * always the earlier operand.  It writes the box fields of every record of the six NodeRec arrays, the child boxes of every pair
+ * record and the root box.  The orderings are NOT re-sorted by the new box centres: a refit tree is walked in the orderings of its
+ * last build.  The first refit after an upload or an update derives the refit plan from the uploaded arrays on the device and
+ * blocks for it; it returns RDH_ERR_STATE (the scene unchanged and usable) unless the six arrays are six orderings of one tree
+ * with one primitive per leaf.  Otherwise asynchronous on the context's stream, like rdh_scene_update_geometry.
+ * rdh_scene_tree_cost: the SAH cost of the tree as it stands, sum over every node of surfaceArea(box) / surfaceArea(root box), in
+ * double by a reduction of fixed order (it repeats exactly), and the same topology's cost before the first refit since the last
+ * upload / update (both equal the current cost before any refit).  A root box of zero surface area (all geometry on one line or
+ * point) makes every node count 1: the cost is then bvhSize.  Their ratio says when to rebuild.  Blocking. */
+int rdh_scene_refit_geometry(rdh_ctx *ctx, const float *d_vertices, const float *d_normals, const rdh_light_update *lights);
+int rdh_scene_tree_cost(rdh_ctx *ctx, double *sahNow, double *sahAtBuild);
 /* Test access to the tree the kernels walk: which = 0 the six NodeRec arrays (6 x (bvhSize + 1) x 32 B, pad records included),
  * 1 the sibling pairs ((bvhSize - 1) / 2 + 1 records of 64 B; 0 bytes when the scene has none), 2 {int32 treeDepth, hasPairs, 0, 0;
  * float rootLo[4]; float rootHi[4]} (48 B).  Returns the byte size (hostOut NULL: only that) or a negative RDH_ERR_*.  Blocking. */

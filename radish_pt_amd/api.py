@@ -56,6 +56,7 @@ EXPORTS = [
     "rdh_comm_init_all", "rdh_path_trace_gathered_all", "rdh_gbuffer_exchange_all", "rdh_restir_direct_gathered_all",
     "rdh_comm_set_overlap", "rdh_comm_join",
     "rdh_build_bvh_device", "rdh_scene_update_geometry", "rdh_debug_read_tree",
+    "rdh_scene_refit_geometry", "rdh_scene_tree_cost",
 ]
 
 
@@ -176,6 +177,8 @@ def lib():
             "rdh_build_bvh_device": ([vp, vp, i32, vp, C.POINTER(vp)], i32),
             "rdh_scene_update_geometry": ([vp, vp, vp, C.POINTER(LightUpdateC)], i32),
             "rdh_debug_read_tree": ([vp, i32, vp, i64], i64),
+            "rdh_scene_refit_geometry": ([vp, vp, vp, C.POINTER(LightUpdateC)], i32),
+            "rdh_scene_tree_cost": ([vp, C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -295,26 +298,44 @@ class Context:
         self.check(lib().rdh_build_bvh_device(self.h, vp, n, boxes.data_ptr(), ptrs))
         return boxes, nodes
 
-    def update_geometry(self, vertices, normals=None, lights=None):
-        """New positions for the uploaded scene's triangles (same count and order): vertices / normals float32 cuda tensors of
-        9*numPrims floats; lights None (keep the light table) or (light_sampler, sum_light_power_inv) with light_sampler a
-        layouts.BINOMIAL_DTYPE array of the scene's length.  Rebuilds the tree on the device; does not block."""
+    def _geometry_args(self, what, vertices, normals, lights):
         n = getattr(self, "_num_prims", None)
         if n is None:
-            raise RadishError("update_geometry: no scene uploaded")
+            raise RadishError(f"{what}: no scene uploaded")
         torch = _torch()
-        for t, what in ((vertices, "vertices"), (normals, "normals")):
+        for t, name in ((vertices, "vertices"), (normals, "normals")):
             if t is not None and (not isinstance(t, torch.Tensor) or t.numel() != 9 * n):
                 got = t.numel() if isinstance(t, torch.Tensor) else type(t).__name__
-                raise RadishError(f"update_geometry: {what} must hold 9*{n} floats (the uploaded triangle count), got {got}")
-        vp = self._ptr(vertices, 9 * n, "update_geometry vertices")
-        np_ = None if normals is None else self._ptr(normals, 9 * n, "update_geometry normals")
+                raise RadishError(f"{what}: {name} must hold 9*{n} floats (the uploaded triangle count), got {got}")
+        vp = self._ptr(vertices, 9 * n, f"{what} vertices")
+        np_ = None if normals is None else self._ptr(normals, 9 * n, f"{what} normals")
         lu = None
         if lights is not None:
             table, inv = lights
             table = np.ascontiguousarray(table, dtype=L.BINOMIAL_DTYPE)
             lu = LightUpdateC(table.ctypes.data if len(table) else None, len(table), float(inv))
+        # the LightUpdateC keeps no reference to the table: return it so that it lives through the call
+        return vp, np_, lu, lights if lights is None else table
+
+    def update_geometry(self, vertices, normals=None, lights=None):
+        """New positions for the uploaded scene's triangles (same count and order): vertices / normals float32 cuda tensors of
+        9*numPrims floats; lights None (keep the light table) or (light_sampler, sum_light_power_inv) with light_sampler a
+        layouts.BINOMIAL_DTYPE array of the scene's length.  Rebuilds the tree on the device; does not block."""
+        vp, np_, lu, _keep = self._geometry_args("update_geometry", vertices, normals, lights)
         self.check(lib().rdh_scene_update_geometry(self.h, vp, np_, None if lu is None else C.byref(lu)))
+
+    def refit_geometry(self, vertices, normals=None, lights=None):
+        """update_geometry's arguments, but the tree keeps its topology and only its boxes are recomputed (rdh_scene_refit_geometry).
+        The first refit after an upload or update_geometry derives the refit plan and blocks; later ones do not block."""
+        vp, np_, lu, _keep = self._geometry_args("refit_geometry", vertices, normals, lights)
+        self.check(lib().rdh_scene_refit_geometry(self.h, vp, np_, None if lu is None else C.byref(lu)))
+
+    def tree_cost(self):
+        """(now, at_build): the SAH cost of the tree as it stands and before the first refit since the last upload / update_geometry
+        (rdh_scene_tree_cost).  Blocking."""
+        now, at_build = C.c_double(0), C.c_double(0)
+        self.check(lib().rdh_scene_tree_cost(self.h, C.byref(now), C.byref(at_build)))
+        return now.value, at_build.value
 
     def debug_read_tree(self, which):
         """Blocking test access (rdh_debug_read_tree): 0 -> NodeRec bytes, 1 -> PairRec bytes, 2 -> the 48-byte header."""

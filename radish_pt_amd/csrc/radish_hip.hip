@@ -25,6 +25,7 @@
 #include "device/kernels_display.h"
 #include "device/kernels_denoise.h"
 #include "device/kernels_bvh.h"
+#include "device/kernels_refit.h"
 
 using namespace rd;
 
@@ -144,6 +145,12 @@ struct rdh_ctx {
     hipEvent_t evAliasStage[2] = {nullptr, nullptr};
     int aliasStageNext = 0;
     hipEvent_t evUpdWait = nullptr;
+
+    // rdh_scene_refit_geometry (kernels_refit.h): the refit plan of the current topology and its workspace, for refitCap primitives
+    void *refitBuf = nullptr;
+    int refitCap = 0;
+    bool planValid = false;  // built by the first refit after an upload / update_geometry; dropped by those and rdh_scene_free
+    bool treeRefit = false;  // the pending tree header (treePending) is a refit's: only the root box changes
 };
 
 namespace {
@@ -366,6 +373,14 @@ int settleTree(rdh_ctx *c) {
     if (!c->treePending) return RDH_OK;
     HIP_TRY(c, hipEventSynchronize(c->evTree));
     c->treePending = false;
+    if (c->treeRefit) {  // same topology: treeDepth, pairs and the root's w stay
+        c->treeRefit = false;
+        if (!c->ds.pairs) return RDH_OK;  // the root box is a pair walk's argument; without pairs the upload leaves it zero too
+        const int4 lo = c->hTreeHdr[1], hi = c->hTreeHdr[2];
+        c->ds.rootLo = make_float4(__builtin_bit_cast(float, lo.x), __builtin_bit_cast(float, lo.y), __builtin_bit_cast(float, lo.z), c->ds.rootLo.w);
+        c->ds.rootHi = make_float4(__builtin_bit_cast(float, hi.x), __builtin_bit_cast(float, hi.y), __builtin_bit_cast(float, hi.z), c->ds.rootHi.w);
+        return RDH_OK;
+    }
     const int4 h0 = c->hTreeHdr[0], lo = c->hTreeHdr[1], hi = c->hTreeHdr[2];
     if (h0.y != 0) {
         c->haveScene = false;
@@ -744,6 +759,8 @@ int rdh_scene_free(rdh_ctx *c) {
     c->sceneAllocs.clear();
     c->haveScene = false;
     c->treePending = false;
+    c->treeRefit = false;
+    c->planValid = false;
     c->dLightPrims = nullptr;
     c->updPairs = nullptr;
     c->numLights = 0;
@@ -766,6 +783,7 @@ void rdh_destroy(rdh_ctx *c) {
         if (c->wfTreeOvf[h]) hipFree(c->wfTreeOvf[h]);
     if (c->bvhScratch) hipFree(c->bvhScratch);
     if (c->updTree) hipFree(c->updTree);
+    if (c->refitBuf) hipFree(c->refitBuf);
     if (c->dTreeHdr) hipFree(c->dTreeHdr);
     if (c->hTreeHdr) hipHostFree(c->hTreeHdr);
     if (c->evTree) hipEventDestroy(c->evTree);
@@ -2424,43 +2442,24 @@ int launchBvhBuild(rdh_ctx *c, BvhWork &w) {
     return RDH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rdh_build_bvh_device(rdh_ctx *c, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]) {
-    if (!c) return RDH_ERR_ARGS;
-    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: bad arguments");
-    for (int k = 0; k < 6; k++)
-        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: d_nodes[%d] is null", k);
-    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: %d primitives", numPrims);
-    HIP_TRY(c, hipSetDevice(c->device));
-    BvhWork w{};
-    int rc = bvhWorkspace(c, numPrims, w);
-    if (rc) return rc;
-    w.verts = d_vertices;
-    w.boxes = d_boxes;
-    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
-    return launchBvhBuild(c, w);
-}
-
-int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
-    if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: no scene uploaded");
-    if (!d_vertices) return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: d_vertices is null");
+// Shared by rdh_scene_update_geometry and rdh_scene_refit_geometry.
+int checkGeomArgs(rdh_ctx *c, const char *what, const float *d_vertices, const rdh_light_update *lights) {
+    if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "%s: no scene uploaded", what);
+    if (!d_vertices) return fail(c, RDH_ERR_ARGS, "%s: d_vertices is null", what);
     if (lights) {
         if (lights->lightSamplerLength != c->ds.lightSamplerLength)
-            return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: lightSamplerLength %d != the scene's %d", lights->lightSamplerLength,
+            return fail(c, RDH_ERR_ARGS, "%s: lightSamplerLength %d != the scene's %d", what, lights->lightSamplerLength,
                         c->ds.lightSamplerLength);
-        if (lights->lightSamplerLength > 0 && !lights->lightSampler)
-            return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: lightSampler is null");
+        if (lights->lightSamplerLength > 0 && !lights->lightSampler) return fail(c, RDH_ERR_ARGS, "%s: lightSampler is null", what);
         const AliasRec *a = static_cast<const AliasRec *>(lights->lightSampler);
         for (int i = 0; i < lights->lightSamplerLength; i++)
             if (a[i].failId < 0 || a[i].failId >= lights->lightSamplerLength)
-                return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry: alias table failId out of range");
+                return fail(c, RDH_ERR_ARGS, "%s: alias table failId out of range", what);
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    return RDH_OK;
+}
+
+int ensureTreeHeader(rdh_ctx *c) {
     if (!c->evTree) {
         HIP_TRY(c, hipEventCreateWithFlags(&c->evTree, hipEventDisableTiming));
         HIP_TRY(c, hipEventCreateWithFlags(&c->evUpdWait, hipEventDisableTiming));
@@ -2468,37 +2467,22 @@ int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *
         HIP_TRY(c, hipMalloc((void **)&c->dTreeHdr, 3 * sizeof(int4)));
         HIP_TRY(c, hipHostMalloc((void **)&c->hTreeHdr, 3 * sizeof(int4), hipHostMallocDefault));
     }
-    // The scene's arrays are rewritten in place: launches still in flight on the side streams read them, so wait for those
+    return RDH_OK;
+}
+
+// The scene's arrays are rewritten in place: launches still in flight on the side streams read them, so wait for those
+int waitSideStreams(rdh_ctx *c) {
     for (hipStream_t side : {c->sideStream, c->litStream, c->wfStream}) {
         if (!side || side == c->stream) continue;
         HIP_TRY(c, hipEventRecord(c->evUpdWait, side));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evUpdWait, 0));
     }
-    if (!c->ds.pairs && !c->updPairs) {  // the upload had no pairs; an updated tree always has them
-        void *p = nullptr;
-        HIP_TRY(c, hipMalloc(&p, sizeof(PairRec) * ((size_t)(S - 1) / 2 + 1)));
-        c->sceneAllocs.push_back(p);
-        c->updPairs = static_cast<PairRec *>(p);
-    }
-    PairRec *pairs = c->updPairs ? c->updPairs : const_cast<PairRec *>(c->ds.pairs);
-    if (N > c->updCap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->updTree) hipFree(c->updTree);
-        c->updTree = nullptr;
-        c->updCap = 0;
-        HIP_TRY(c, hipMalloc(&c->updTree, alignUp(sizeof(float) * 6 * (size_t)S) + 6 * alignUp(sizeof(int) * 3 * (size_t)S)));
-        c->updCap = N;
-    }
-    BvhWork w{};
-    int rc = bvhWorkspace(c, N, w);
-    if (rc) return rc;
-    char *t = static_cast<char *>(c->updTree);
-    w.verts = d_vertices;
-    w.boxes = reinterpret_cast<float *>(t);
-    for (int k = 0; k < 6; k++)
-        w.nodes[k] = reinterpret_cast<int *>(t + alignUp(sizeof(float) * 6 * (size_t)S) + k * alignUp(sizeof(int) * 3 * (size_t)S));
+    return RDH_OK;
+}
 
-    // triangles, attributes, emissive triangles
+// Triangles, attributes, emissive triangles, the light table and the per-light constants, on the context's stream.
+int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
+    const int N = c->ds.numPrims;
     const int geomN = std::max(N, c->numLights);
     hipLaunchKernelGGL(k_geom_update, dim3((unsigned)((geomN + 255) / 256)), dim3(256), 0, c->stream, d_vertices, d_normals,
                        const_cast<TriRec *>(c->ds.tris), const_cast<AttrRec *>(c->ds.attrs), N, const_cast<LightRec *>(c->ds.lights),
@@ -2523,6 +2507,62 @@ int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *
     if (c->numLights > 0)
         hipLaunchKernelGGL(k_light_precompute, dim3((unsigned)((c->numLights + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights,
                            const_cast<LightPre *>(c->ds.lightPre), c->numLights, c->ds.sumLightPowerInv);
+    return RDH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_build_bvh_device(rdh_ctx *c, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: bad arguments");
+    for (int k = 0; k < 6; k++)
+        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: d_nodes[%d] is null", k);
+    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: %d primitives", numPrims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    BvhWork w{};
+    int rc = bvhWorkspace(c, numPrims, w);
+    if (rc) return rc;
+    w.verts = d_vertices;
+    w.boxes = d_boxes;
+    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
+    return launchBvhBuild(c, w);
+}
+
+int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
+    if (!c) return RDH_ERR_ARGS;
+    int rc = checkGeomArgs(c, "rdh_scene_update_geometry", d_vertices, lights);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    if ((rc = ensureTreeHeader(c))) return rc;
+    if ((rc = waitSideStreams(c))) return rc;
+    c->planValid = false;  // a new topology: the next refit derives its plan again
+    if (!c->ds.pairs && !c->updPairs) {  // the upload had no pairs; an updated tree always has them
+        void *p = nullptr;
+        HIP_TRY(c, hipMalloc(&p, sizeof(PairRec) * ((size_t)(S - 1) / 2 + 1)));
+        c->sceneAllocs.push_back(p);
+        c->updPairs = static_cast<PairRec *>(p);
+    }
+    PairRec *pairs = c->updPairs ? c->updPairs : const_cast<PairRec *>(c->ds.pairs);
+    if (N > c->updCap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->updTree) hipFree(c->updTree);
+        c->updTree = nullptr;
+        c->updCap = 0;
+        HIP_TRY(c, hipMalloc(&c->updTree, alignUp(sizeof(float) * 6 * (size_t)S) + 6 * alignUp(sizeof(int) * 3 * (size_t)S)));
+        c->updCap = N;
+    }
+    BvhWork w{};
+    if ((rc = bvhWorkspace(c, N, w))) return rc;
+    char *t = static_cast<char *>(c->updTree);
+    w.verts = d_vertices;
+    w.boxes = reinterpret_cast<float *>(t);
+    for (int k = 0; k < 6; k++)
+        w.nodes[k] = reinterpret_cast<int *>(t + alignUp(sizeof(float) * 6 * (size_t)S) + k * alignUp(sizeof(int) * 3 * (size_t)S));
+
+    if ((rc = rewriteGeometry(c, d_vertices, d_normals, lights))) return rc;
 
     // the tree and what the upload derives from it
     if ((rc = launchBvhBuild(c, w))) return rc;
@@ -2534,7 +2574,150 @@ int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *
     HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr, c->dTreeHdr, 3 * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->evTree, c->stream));
     c->treePending = true;
+    c->treeRefit = false;  // this header is an update's (a refit's header still pending is superseded): settle all of it
     c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
+    return RDH_OK;
+}
+
+}  // extern "C"
+
+// ---- refit of the uploaded tree (kernels_refit.h) ---------------------------------------------------------------------------------
+namespace {
+
+struct RefitWork {  // carved from rdh_ctx::refitBuf for refitCap primitives; the arrival counters come first (one memset block)
+    int *counters;        // S
+    RefitPlanRec *plan;   // S
+    int *parentCount;     // S
+    int *primPos;         // 6 N
+    int *blockSums;       // ceil(S / 256)
+    int *err;
+    double *partial;      // kCostBlocks
+    double *cost;         // [0] now, [1] at build
+    float4 *rootBox;      // lo, hi
+};
+
+int refitWork(rdh_ctx *c, RefitWork &r) {
+    const int N = c->ds.numPrims;
+    const size_t S = 2 * (size_t)N - 1, blocks = (S + 255) / 256;
+    const size_t sz[9] = {alignUp(4 * S), alignUp(sizeof(RefitPlanRec) * S), alignUp(4 * S), alignUp(4 * 6 * (size_t)N), alignUp(4 * blocks),
+                          256, alignUp(8 * kCostBlocks), 256, 256};
+    if (N > c->refitCap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->refitBuf) hipFree(c->refitBuf);
+        c->refitBuf = nullptr;
+        c->refitCap = 0;
+        size_t total = 0;
+        for (size_t x : sz) total += x;
+        HIP_TRY(c, hipMalloc(&c->refitBuf, total));
+        c->refitCap = N;
+    }
+    char *p = static_cast<char *>(c->refitBuf);
+    void *part[9];
+    for (int i = 0; i < 9; i++) {
+        part[i] = p;
+        p += sz[i];
+    }
+    r.counters = static_cast<int *>(part[0]);
+    r.plan = static_cast<RefitPlanRec *>(part[1]);
+    r.parentCount = static_cast<int *>(part[2]);
+    r.primPos = static_cast<int *>(part[3]);
+    r.blockSums = static_cast<int *>(part[4]);
+    r.err = static_cast<int *>(part[5]);
+    r.partial = static_cast<double *>(part[6]);
+    r.cost = static_cast<double *>(part[7]);
+    r.rootBox = static_cast<float4 *>(part[8]);
+    return RDH_OK;
+}
+
+int launchTreeCost(rdh_ctx *c, const RefitWork &r, int slot) {
+    hipLaunchKernelGGL(k_tree_cost_partial, dim3(kCostBlocks), dim3(256), 0, c->stream, c->ds.nodes[0], c->ds.bvhSize, r.partial);
+    hipLaunchKernelGGL(k_tree_cost_final, dim3(1), dim3(256), 0, c->stream, c->ds.nodes[0], (const double *)r.partial, c->ds.bvhSize,
+                       r.cost + slot);
+    HIP_TRY(c, hipGetLastError());
+    return RDH_OK;
+}
+
+// The refit plan of the uploaded topology, derived from the six NodeRec arrays on the device, and the tree's cost as it stands
+// (sahAtBuild).  Blocking: the caller learns here whether the arrays are one tree.
+int buildRefitPlan(rdh_ctx *c, RefitWork &r) {
+    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    const unsigned grid = (unsigned)((S + 255) / 256);
+    HIP_TRY(c, hipMemsetAsync(r.counters, 0, 4 * (size_t)S, c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.plan, 0xff, sizeof(RefitPlanRec) * (size_t)S, c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.parentCount, 0, 4 * (size_t)S, c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.primPos, 0xff, 4 * 6 * (size_t)N, c->stream));
+    HIP_TRY(c, hipMemsetAsync(r.err, 0, 4, c->stream));
+    hipLaunchKernelGGL(k_refit_links, dim3((unsigned)((6ll * S + 255) / 256)), dim3(256), 0, c->stream, c->ds.nodes[0], S, N, r.plan,
+                       r.parentCount, r.primPos, r.err);
+    hipLaunchKernelGGL(k_refit_count, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, r.blockSums);
+    hipLaunchKernelGGL(k_refit_scan, dim3(1), dim3(256), 0, c->stream, r.blockSums, (int)grid);
+    hipLaunchKernelGGL(k_refit_number, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, (const int *)r.blockSums, r.plan);
+    hipLaunchKernelGGL(k_refit_plan_climb, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, N, r.plan, (const int *)r.primPos,
+                       r.counters, r.err);
+    hipLaunchKernelGGL(k_refit_check, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, (const RefitPlanRec *)r.plan,
+                       (const int *)r.parentCount, c->ds.pairs, r.err);
+    HIP_TRY(c, hipGetLastError());
+    int rc = launchTreeCost(c, r, 1);
+    if (rc) return rc;
+    int err = 0;
+    HIP_TRY(c, hipMemcpyAsync(&err, r.err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (err)
+        return fail(c, RDH_ERR_STATE,
+                    "rdh_scene_refit_geometry: the scene's six node arrays are not six orderings of one tree with one primitive per "
+                    "leaf (check bits %d); upload the scene again or call rdh_scene_update_geometry", err);
+    c->planValid = true;
+    return RDH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_scene_refit_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
+    if (!c) return RDH_ERR_ARGS;
+    int rc = checkGeomArgs(c, "rdh_scene_refit_geometry", d_vertices, lights);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensureTreeHeader(c))) return rc;
+    RefitWork r{};
+    if (!c->planValid) {
+        if ((rc = settleTree(c))) return rc;  // the plan reads the update's tree; its header must be folded in first
+        if ((rc = refitWork(c, r))) return rc;
+        if ((rc = buildRefitPlan(c, r))) return rc;  // nothing has changed yet when this refuses
+    } else if ((rc = refitWork(c, r))) {
+        return rc;
+    }
+    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    if ((rc = waitSideStreams(c))) return rc;
+    if ((rc = rewriteGeometry(c, d_vertices, d_normals, lights))) return rc;
+    HIP_TRY(c, hipMemsetAsync(r.counters, 0, 4 * (size_t)std::max(N - 1, 1), c->stream));
+    hipLaunchKernelGGL(k_refit, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, d_vertices, (const RefitPlanRec *)r.plan,
+                       const_cast<NodeRec *>(c->ds.nodes[0]), const_cast<PairRec *>(c->ds.pairs), r.counters, r.rootBox, S);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr + 1, r.rootBox, 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evTree, c->stream));
+    c->treePending = true;
+    c->treeRefit = true;
+    c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
+    return RDH_OK;
+}
+
+int rdh_scene_tree_cost(rdh_ctx *c, double *sahNow, double *sahAtBuild) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!sahNow || !sahAtBuild) return fail(c, RDH_ERR_ARGS, "rdh_scene_tree_cost: null output");
+    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_tree_cost: no scene uploaded");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = settleTree(c);
+    if (rc) return rc;
+    RefitWork r{};
+    if ((rc = refitWork(c, r))) return rc;
+    if ((rc = launchTreeCost(c, r, 0))) return rc;
+    double cost[2] = {0.0, 0.0};
+    HIP_TRY(c, hipMemcpyAsync(cost, r.cost, sizeof(cost), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *sahNow = cost[0];
+    *sahAtBuild = c->planValid ? cost[1] : cost[0];
     return RDH_OK;
 }
 
