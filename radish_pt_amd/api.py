@@ -41,6 +41,9 @@ RDH_PT_NO_PAIRS = 16384
 RDH_PT_NO_PACKETS = 8192
 RDH_PT_PAIRS = 32768
 RDH_PT_AUTO = 65536
+# BVH builders of rdh_build_bvh_device_ex / rdh_scene_update_geometry_ex (Context.build_bvh_device / update_geometry `builder`)
+RDH_BVH_SAH, RDH_BVH_LBVH = 0, 1
+BVH_BUILDERS = {"sah": RDH_BVH_SAH, "lbvh": RDH_BVH_LBVH}
 SOBOL_SAMPLE_NUM = 10000  # SobolSampleNum, src/sampler.h:12
 
 # Every symbol include/radish_hip.h declares (tests check that the library exports all of them).
@@ -57,6 +60,7 @@ EXPORTS = [
     "rdh_comm_set_overlap", "rdh_comm_join",
     "rdh_build_bvh_device", "rdh_scene_update_geometry", "rdh_debug_read_tree",
     "rdh_scene_refit_geometry", "rdh_scene_tree_cost",
+    "rdh_build_bvh_device_ex", "rdh_scene_update_geometry_ex",
 ]
 
 
@@ -179,6 +183,8 @@ def lib():
             "rdh_debug_read_tree": ([vp, i32, vp, i64], i64),
             "rdh_scene_refit_geometry": ([vp, vp, vp, C.POINTER(LightUpdateC)], i32),
             "rdh_scene_tree_cost": ([vp, C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
+            "rdh_build_bvh_device_ex": ([vp, vp, i32, i32, vp, C.POINTER(vp)], i32),
+            "rdh_scene_update_geometry_ex": ([vp, vp, vp, C.POINTER(LightUpdateC), i32], i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -195,6 +201,13 @@ def _torch():
     import torch
 
     return torch
+
+
+def _builder(what, builder):
+    """A builder name of BVH_BUILDERS -> its RDH_BVH_* value."""
+    if builder not in BVH_BUILDERS:
+        raise RadishError(f"{what}: builder must be one of {sorted(BVH_BUILDERS)}, got {builder!r}")
+    return BVH_BUILDERS[builder]
 
 
 class Context:
@@ -283,9 +296,11 @@ class Context:
         self._num_prims = int(sd.num_prims)
 
     # ---- moving geometry: the device BVH builder ----
-    def build_bvh_device(self, vertices):
-        """vertices: float32 cuda tensor [3N, 3] (or [N, 3, 3]) -> (boxes float32 [2N-1, 6], nodes int32 [6, 2N-1, 3]) on the device,
-        bit for bit hostlib.build_bvh of the same soup.  Asynchronous on the context's stream."""
+    def build_bvh_device(self, vertices, builder="sah"):
+        """vertices: float32 cuda tensor [3N, 3] (or [N, 3, 3]) -> (boxes float32 [2N-1, 6], nodes int32 [6, 2N-1, 3]) on the device.
+        builder "sah": bit for bit hostlib.build_bvh of the same soup; "lbvh": the linear BVH (rdh_build_bvh_device_ex).
+        Asynchronous on the context's stream."""
+        b = _builder("build_bvh_device", builder)
         torch = _torch()
         if not isinstance(vertices, torch.Tensor) or vertices.numel() == 0 or vertices.numel() % 9:
             raise RadishError("build_bvh_device: vertices must be a tensor of 9*N floats (N >= 1)")
@@ -295,7 +310,10 @@ class Context:
         boxes = torch.empty(size, 6, dtype=torch.float32, device=vertices.device)
         nodes = torch.empty(6, size, 3, dtype=torch.int32, device=vertices.device)
         ptrs = (C.c_void_p * 6)(*[nodes[k].data_ptr() for k in range(6)])
-        self.check(lib().rdh_build_bvh_device(self.h, vp, n, boxes.data_ptr(), ptrs))
+        if b == RDH_BVH_SAH:
+            self.check(lib().rdh_build_bvh_device(self.h, vp, n, boxes.data_ptr(), ptrs))
+        else:
+            self.check(lib().rdh_build_bvh_device_ex(self.h, vp, n, b, boxes.data_ptr(), ptrs))
         return boxes, nodes
 
     def _geometry_args(self, what, vertices, normals, lights):
@@ -317,12 +335,17 @@ class Context:
         # the LightUpdateC keeps no reference to the table: return it so that it lives through the call
         return vp, np_, lu, lights if lights is None else table
 
-    def update_geometry(self, vertices, normals=None, lights=None):
+    def update_geometry(self, vertices, normals=None, lights=None, builder="sah"):
         """New positions for the uploaded scene's triangles (same count and order): vertices / normals float32 cuda tensors of
         9*numPrims floats; lights None (keep the light table) or (light_sampler, sum_light_power_inv) with light_sampler a
-        layouts.BINOMIAL_DTYPE array of the scene's length.  Rebuilds the tree on the device; does not block."""
+        layouts.BINOMIAL_DTYPE array of the scene's length.  Rebuilds the tree on the device with `builder` ("sah": the host
+        builder's tree; "lbvh": the linear BVH); does not block."""
+        b = _builder("update_geometry", builder)
         vp, np_, lu, _keep = self._geometry_args("update_geometry", vertices, normals, lights)
-        self.check(lib().rdh_scene_update_geometry(self.h, vp, np_, None if lu is None else C.byref(lu)))
+        if b == RDH_BVH_SAH:
+            self.check(lib().rdh_scene_update_geometry(self.h, vp, np_, None if lu is None else C.byref(lu)))
+        else:
+            self.check(lib().rdh_scene_update_geometry_ex(self.h, vp, np_, None if lu is None else C.byref(lu), b))
 
     def refit_geometry(self, vertices, normals=None, lights=None):
         """update_geometry's arguments, but the tree keeps its topology and only its boxes are recomputed (rdh_scene_refit_geometry).

@@ -26,6 +26,7 @@
 #include "device/kernels_denoise.h"
 #include "device/kernels_bvh.h"
 #include "device/kernels_refit.h"
+#include "device/kernels_lbvh.h"
 
 using namespace rd;
 
@@ -131,6 +132,8 @@ struct rdh_ctx {
     // device BVH builder (kernels_bvh.h) and rdh_scene_update_geometry
     void *bvhScratch = nullptr;      // BvhWork buffers for bvhCap primitives, one allocation
     int bvhCap = 0;
+    void *lbvhScratch = nullptr;     // LbvhWork buffers and the BvhWork slot arrays for lbvhCap primitives (RDH_BVH_LBVH)
+    int lbvhCap = 0;
     void *updTree = nullptr;         // the update's boxes + six int[S][3] orderings, for updCap primitives
     int updCap = 0;
     int *dLightPrims = nullptr;      // the uploaded scene's lightPrimIds (scene allocation)
@@ -782,6 +785,7 @@ void rdh_destroy(rdh_ctx *c) {
     for (int h = 0; h < 3; h++)
         if (c->wfTreeOvf[h]) hipFree(c->wfTreeOvf[h]);
     if (c->bvhScratch) hipFree(c->bvhScratch);
+    if (c->lbvhScratch) hipFree(c->lbvhScratch);
     if (c->updTree) hipFree(c->updTree);
     if (c->refitBuf) hipFree(c->refitBuf);
     if (c->dTreeHdr) hipFree(c->dTreeHdr);
@@ -2442,6 +2446,75 @@ int launchBvhBuild(rdh_ctx *c, BvhWork &w) {
     return RDH_OK;
 }
 
+// Workspace of the LBVH builder (kernels_lbvh.h) for N primitives, and the BvhWork slot arrays it fills (grown on demand, kept by
+// the context); the BvhWork outputs (boxes, nodes) are filled in by the caller.
+int lbvhWorkspace(rdh_ctx *c, int N, LbvhWork &L, BvhWork &w) {
+    const size_t S = 2 * (size_t)N - 1, inner = std::max(N - 1, 1), tiles = ((size_t)N + kLbvhTile - 1) / kLbvhTile;
+    const size_t sz[13] = {alignUp(sizeof(float4) * 2 * (size_t)N), alignUp(sizeof(float) * 6 * (kLbvhBlocks + 1)),
+                           alignUp(4 * (size_t)N), alignUp(4 * (size_t)N), alignUp(4 * (size_t)N), alignUp(4 * (size_t)N),
+                           alignUp(4 * 256 * tiles), alignUp(sizeof(int4) * S), alignUp(sizeof(int2) * inner),
+                           alignUp(sizeof(float) * 8 * S), alignUp(4 * inner), alignUp(4 * 3 * S), 256};
+    if (N > c->lbvhCap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->lbvhScratch) hipFree(c->lbvhScratch);
+        c->lbvhScratch = nullptr;
+        c->lbvhCap = 0;
+        size_t total = 0;
+        for (size_t x : sz) total += x;
+        HIP_TRY(c, hipMalloc(&c->lbvhScratch, total));
+        c->lbvhCap = N;
+    }
+    char *p = static_cast<char *>(c->lbvhScratch);
+    void *part[13];
+    for (int i = 0; i < 13; i++) {
+        part[i] = p;
+        p += sz[i];
+    }
+    L.leafBox = static_cast<float4 *>(part[0]);
+    L.bounds = static_cast<float *>(part[1]);
+    L.keys[0] = static_cast<unsigned *>(part[2]);
+    L.keys[1] = static_cast<unsigned *>(part[3]);
+    L.vals[0] = static_cast<int *>(part[4]);
+    L.vals[1] = static_cast<int *>(part[5]);
+    L.hist = static_cast<int *>(part[6]);
+    L.rec = static_cast<int4 *>(part[7]);
+    L.child = static_cast<int2 *>(part[8]);
+    L.nodeBox = static_cast<float *>(part[9]);
+    L.counters = static_cast<int *>(part[10]);
+    L.numPrims = N;
+    L.numTiles = (int)tiles;
+    w.info = static_cast<int *>(part[11]);
+    w.bits = w.info + S;
+    w.qnum = w.info + 2 * S;
+    w.ctl = static_cast<int *>(part[12]);
+    w.numPrims = N;
+    return RDH_OK;
+}
+
+// Builds the LBVH tree of L.verts into w's outputs on the context's stream (no host synchronisation).
+int launchLbvhBuild(rdh_ctx *c, LbvhWork &L, BvhWork &w) {
+    const int N = L.numPrims, S = 2 * N - 1;
+    const unsigned primGrid = (unsigned)((N + 255) / 256);
+    HIP_TRY(c, hipMemsetAsync(w.ctl, 0, 8 * sizeof(int), c->stream));
+    HIP_TRY(c, hipMemsetAsync(L.counters, 0, 4 * (size_t)std::max(N - 1, 1), c->stream));
+    hipLaunchKernelGGL(k_lbvh_leaves, dim3(kLbvhBlocks), dim3(256), 0, c->stream, L);
+    hipLaunchKernelGGL(k_lbvh_bounds, dim3(1), dim3(256), 0, c->stream, L);
+    hipLaunchKernelGGL(k_lbvh_codes, dim3(primGrid), dim3(256), 0, c->stream, L);
+    for (int pass = 0; pass < 4; pass++) {  // 30-bit keys, 8-bit digits: four passes, ending in keys[0] / vals[0]
+        const int in = pass & 1, shift = 8 * pass;
+        hipLaunchKernelGGL(k_lbvh_hist, dim3((unsigned)L.numTiles), dim3(256), 0, c->stream, (const unsigned *)L.keys[in], N, shift,
+                           L.hist, L.numTiles);
+        hipLaunchKernelGGL(k_lbvh_scan, dim3(1), dim3(kLbvhScanThreads), 0, c->stream, L.hist, 256 * L.numTiles);
+        hipLaunchKernelGGL(k_lbvh_scatter, dim3((unsigned)L.numTiles), dim3(256), 0, c->stream, (const unsigned *)L.keys[in],
+                           (const int *)L.vals[in], L.keys[in ^ 1], L.vals[in ^ 1], N, shift, (const int *)L.hist, L.numTiles);
+    }
+    hipLaunchKernelGGL(k_lbvh_karras, dim3((unsigned)((std::max(N - 1, 1) + 255) / 256)), dim3(256), 0, c->stream, L, w.ctl);
+    hipLaunchKernelGGL(k_lbvh_up, dim3(primGrid), dim3(256), 0, c->stream, L, w.ctl);
+    hipLaunchKernelGGL(k_lbvh_place, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, L, w);
+    HIP_TRY(c, hipGetLastError());
+    return RDH_OK;
+}
+
 // Shared by rdh_scene_update_geometry and rdh_scene_refit_geometry.
 int checkGeomArgs(rdh_ctx *c, const char *what, const float *d_vertices, const rdh_light_update *lights) {
     if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "%s: no scene uploaded", what);
@@ -2510,29 +2583,11 @@ int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals,
     return RDH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rdh_build_bvh_device(rdh_ctx *c, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]) {
+// rdh_scene_update_geometry(_ex): the tree of `builder` (RDH_BVH_SAH or RDH_BVH_LBVH, checked by the caller).
+int updateGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights, int builder,
+                   const char *what) {
     if (!c) return RDH_ERR_ARGS;
-    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: bad arguments");
-    for (int k = 0; k < 6; k++)
-        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: d_nodes[%d] is null", k);
-    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: %d primitives", numPrims);
-    HIP_TRY(c, hipSetDevice(c->device));
-    BvhWork w{};
-    int rc = bvhWorkspace(c, numPrims, w);
-    if (rc) return rc;
-    w.verts = d_vertices;
-    w.boxes = d_boxes;
-    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
-    return launchBvhBuild(c, w);
-}
-
-int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
-    if (!c) return RDH_ERR_ARGS;
-    int rc = checkGeomArgs(c, "rdh_scene_update_geometry", d_vertices, lights);
+    int rc = checkGeomArgs(c, what, d_vertices, lights);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const int N = c->ds.numPrims, S = c->ds.bvhSize;
@@ -2555,7 +2610,9 @@ int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *
         c->updCap = N;
     }
     BvhWork w{};
-    if ((rc = bvhWorkspace(c, N, w))) return rc;
+    LbvhWork L{};
+    if ((rc = builder == RDH_BVH_LBVH ? lbvhWorkspace(c, N, L, w) : bvhWorkspace(c, N, w))) return rc;
+    L.verts = d_vertices;
     char *t = static_cast<char *>(c->updTree);
     w.verts = d_vertices;
     w.boxes = reinterpret_cast<float *>(t);
@@ -2565,7 +2622,7 @@ int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *
     if ((rc = rewriteGeometry(c, d_vertices, d_normals, lights))) return rc;
 
     // the tree and what the upload derives from it
-    if ((rc = launchBvhBuild(c, w))) return rc;
+    if ((rc = builder == RDH_BVH_LBVH ? launchLbvhBuild(c, L, w) : launchBvhBuild(c, w))) return rc;
     const long long recs = 6ll * (S + 1);
     hipLaunchKernelGGL(k_bvh_noderecs, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, c->stream, (const float *)w.boxes, w,
                        const_cast<NodeRec *>(c->ds.nodes[0]), S);
@@ -2577,6 +2634,58 @@ int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *
     c->treeRefit = false;  // this header is an update's (a refit's header still pending is superseded): settle all of it
     c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
     return RDH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_build_bvh_device(rdh_ctx *c, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: bad arguments");
+    for (int k = 0; k < 6; k++)
+        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: d_nodes[%d] is null", k);
+    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: %d primitives", numPrims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    BvhWork w{};
+    int rc = bvhWorkspace(c, numPrims, w);
+    if (rc) return rc;
+    w.verts = d_vertices;
+    w.boxes = d_boxes;
+    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
+    return launchBvhBuild(c, w);
+}
+
+int rdh_build_bvh_device_ex(rdh_ctx *c, const float *d_vertices, int32_t numPrims, int builder, float *d_boxes,
+                            int32_t *const d_nodes[6]) {
+    if (!c) return RDH_ERR_ARGS;
+    if (builder == RDH_BVH_SAH) return rdh_build_bvh_device(c, d_vertices, numPrims, d_boxes, d_nodes);
+    if (builder != RDH_BVH_LBVH) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: unknown builder %d", builder);
+    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: bad arguments");
+    for (int k = 0; k < 6; k++)
+        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: d_nodes[%d] is null", k);
+    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: %d primitives", numPrims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    LbvhWork L{};
+    BvhWork w{};
+    int rc = lbvhWorkspace(c, numPrims, L, w);
+    if (rc) return rc;
+    L.verts = w.verts = d_vertices;
+    w.boxes = d_boxes;
+    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
+    return launchLbvhBuild(c, L, w);
+}
+
+int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
+    return updateGeometry(c, d_vertices, d_normals, lights, RDH_BVH_SAH, "rdh_scene_update_geometry");
+}
+
+int rdh_scene_update_geometry_ex(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights,
+                                 int builder) {
+    if (!c) return RDH_ERR_ARGS;
+    if (builder != RDH_BVH_SAH && builder != RDH_BVH_LBVH)
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_update_geometry_ex: unknown builder %d", builder);
+    return updateGeometry(c, d_vertices, d_normals, lights, builder, "rdh_scene_update_geometry_ex");
 }
 
 }  // extern "C"
