@@ -187,11 +187,14 @@ RD_DEV DenoiseTile denoiseTile(int width, int height, int level) {
     t.v0 = (int(blockIdx.y) % tilesY) * kDT;
     return t;
 }
-// grid of the tiled filters: tiles of every residue class (host side)
+// grid of the tiled filters: tiles of every residue class that holds a pixel (host side).  Levels 0-16 are accepted; once
+// step = 2^level exceeds the image, the classes rx >= width (ry >= height) are empty and not launched, so the grid never
+// exceeds 4 W H workgroups (launching all step^2 classes made level 16 on a 1x1 image 2^32 workgroups).
 inline dim3 denoiseTileGrid(int width, int height, int level) {
     const int step = 1 << level;
     const int subW = (width + step - 1) / step, subH = (height + step - 1) / step;
-    return dim3((unsigned)(((subW + kDT - 1) / kDT) * step), (unsigned)(((subH + kDT - 1) / kDT) * step));
+    const int classesX = step < width ? step : width, classesY = step < height ? step : height;
+    return dim3((unsigned)(((subW + kDT - 1) / kDT) * classesX), (unsigned)(((subH + kDT - 1) / kDT) * classesY));
 }
 
 // EAW: every weight is SYMMETRIC — w(p, q) = min(1, e^(-|cP - cQ|^2 / sL)) min(1, e^(-|nP - nQ|^2 / sN)) min(1, e^(-|xP - xQ|^2 / sD)) g(q - p),
