@@ -206,6 +206,19 @@ int rdh_scene_update_geometry_ex(rdh_ctx *ctx, const float *d_vertices, const fl
  * point) makes every node count 1: the cost is then bvhSize.  Their ratio says when to rebuild.  Blocking. */
 int rdh_scene_refit_geometry(rdh_ctx *ctx, const float *d_vertices, const float *d_normals, const rdh_light_update *lights);
 int rdh_scene_tree_cost(rdh_ctx *ctx, double *sahNow, double *sahAtBuild);
+/* rdh_scene_track_motion: make the G-buffer's motion plane follow geometry that moved.  The reference projects the
+ * CURRENT hit position into the last camera, which names the wrong pixel of last frame's planes once a triangle has moved.  While
+ * tracking is on, the context keeps the triangle records as its most recent rdh_gbuffer_render saw them (48 B per triangle: 48 MB
+ * for config 5's 1-M-triangle scene), and a render after an update projects the hit point's PREVIOUS position (the same
+ * barycentrics on the previous vertices) instead.  enable != 0 allocates the buffer and marks "previous == current"; 0 frees it;
+ * the same value twice is a no-op.  Needs an uploaded scene (RDH_ERR_NO_SCENE); rdh_scene_upload and rdh_scene_free switch it
+ * off.  "Previous" is what was in force at this context's last rdh_gbuffer_render: the first rdh_scene_update_geometry[_ex] /
+ * rdh_scene_refit_geometry after a render saves the records it overwrites (in the same kernel), later ones before the next
+ * render save nothing, and an update that is refused saves nothing.  A render with no update since the last one reads nothing and
+ * writes the reference's plane.  Off (the default): no buffer, the same kernels' output bit for bit.  Misses keep motion = 0; the
+ * plane stays an integer pixel index (-1: out of last frame).  Everything is enqueued on the context's stream; no host wait except
+ * when switching off. */
+int rdh_scene_track_motion(rdh_ctx *ctx, int enable);
 /* Test access to the tree the kernels walk: which = 0 the six NodeRec arrays (6 x (bvhSize + 1) x 32 B, pad records included),
  * 1 the sibling pairs ((bvhSize - 1) / 2 + 1 records of 64 B; 0 bytes when the scene has none), 2 {int32 treeDepth, hasPairs, 0, 0;
  * float rootLo[4]; float rootHi[4]} (48 B).  Returns the byte size (hostOut NULL: only that) or a negative RDH_ERR_*.  Blocking. */

@@ -61,6 +61,7 @@ EXPORTS = [
     "rdh_build_bvh_device", "rdh_scene_update_geometry", "rdh_debug_read_tree",
     "rdh_scene_refit_geometry", "rdh_scene_tree_cost",
     "rdh_build_bvh_device_ex", "rdh_scene_update_geometry_ex",
+    "rdh_scene_track_motion",
 ]
 
 
@@ -185,6 +186,7 @@ def lib():
             "rdh_scene_tree_cost": ([vp, C.POINTER(C.c_double), C.POINTER(C.c_double)], i32),
             "rdh_build_bvh_device_ex": ([vp, vp, i32, i32, vp, C.POINTER(vp)], i32),
             "rdh_scene_update_geometry_ex": ([vp, vp, vp, C.POINTER(LightUpdateC), i32], i32),
+            "rdh_scene_track_motion": ([vp, i32], i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -352,6 +354,12 @@ class Context:
         The first refit after an upload or update_geometry derives the refit plan and blocks; later ones do not block."""
         vp, np_, lu, _keep = self._geometry_args("refit_geometry", vertices, normals, lights)
         self.check(lib().rdh_scene_refit_geometry(self.h, vp, np_, None if lu is None else C.byref(lu)))
+
+    def track_motion(self, enable=True):
+        """Keep the triangle records as this context's last gbuffer_render saw them (48 B per triangle), so that a render after
+        update_geometry / refit_geometry writes motion indices that follow the moved geometry (rdh_scene_track_motion, DESIGN
+        11d).  Needs an uploaded scene; upload_scene switches it off again.  False frees the buffer."""
+        self.check(lib().rdh_scene_track_motion(self.h, 1 if enable else 0))
 
     def tree_cost(self):
         """(now, at_build): the SAH cost of the tree as it stands and before the first refit since the last upload / update_geometry

@@ -496,13 +496,22 @@ __global__ __launch_bounds__(256) void k_bvh_pairs(BvhWork w, PairRec *__restric
 }
 
 // New positions for the same triangles: TriRec (material id kept), AttrRec (texcoords kept; only when normals are given) and the
-// emissive triangles' LightRecs (radiance kept).
+// emissive triangles' LightRecs (radiance kept).  With `prevTris` (rdh_scene_track_motion) the record that is about to be
+// overwritten is kept there first: the positions the last G-buffer render saw, for the motion plane.
 __global__ __launch_bounds__(256) void k_geom_update(const float *__restrict__ verts, const float *__restrict__ normals, TriRec *tris,
-                                                     AttrRec *attrs, int N, LightRec *lights, const int *__restrict__ lightPrims, int numLights) {
+                                                     AttrRec *attrs, int N, LightRec *lights, const int *__restrict__ lightPrims, int numLights,
+                                                     TriRec *__restrict__ prevTris) {
     const int i = int(blockIdx.x * blockDim.x + threadIdx.x);
     if (i < N) {
         const float *v = verts + 9 * (size_t)i;
-        const float mid = tris[i].c.y;
+        float mid;
+        if (prevTris) {
+            const TriRec old = tris[i];
+            prevTris[i] = old;
+            mid = old.c.y;
+        } else {
+            mid = tris[i].c.y;
+        }
         tris[i].a = make_float4(v[0], v[1], v[2], v[3]);
         tris[i].b = make_float4(v[4], v[5], v[6], v[7]);
         tris[i].c = make_float4(v[8], mid, 0.f, 0.f);

@@ -676,6 +676,8 @@ RD_DEV void gbufStore(const DScene &s, const DCamera &cam, const DCamera &lastCa
     if (hitPrim != -1) {
         Surface isec;
         fetchSurface(s, hitPrim, hitBary, isec);
+        // first, while prim and bary are live anyway: kept to the end they cost k_gbuffer_packet its seventh wave (75 VGPRs for 72)
+        gb.motion[idx] = gbufMotionIndex(cam, lastCam, gb, isec, hitBary);
         int matId = isec.matId;
         if (loadMaterial(s.mats, isec.matId).type == Light) matId = -2;  // NullPrimitive - 1 (gBuffer.cu:33-37)
         Material material = texturedMaterial(s, isec);                  // :44 (may perturb isec.norm)
@@ -683,9 +685,6 @@ RD_DEV void gbufStore(const DScene &s, const DCamera &cam, const DCamera &lastCa
         store3(gb.normal, idx, isec.norm);
         gb.primId[idx] = matId;
         gb.depth[idx] = length(rs.o - isec.pos);
-        v2 ndc = cameraRasterUV(lastCam, isec.pos);
-        int lx = (int)(float(lastCam.resx) * ndc.x), ly = (int)(float(lastCam.resy) * ndc.y);
-        gb.motion[idx] = (lx >= 0 && lx < gb.width && ly >= 0 && ly < gb.height) ? ly * cam.resx + lx : -1;
     } else {
         store3(gb.albedo, idx, hasEnvMap(s) ? envLookup(s, rs.d) : mk3(0.f));  // :61-66
         store3(gb.normal, idx, mk3(0.f));

@@ -283,7 +283,23 @@ struct GBufPtrs {
     float *depth;
     int *primId;
     int width, height;
+    const TriRec *prevTris;  // rdh_scene_track_motion: the triangles as the last G-buffer render saw them; null = they have not moved
 };
+// The motion plane's entry of a hit pixel (gBuffer.cu:53-59): the pixel of the LAST camera that saw this surface point.  The
+// reference projects the hit position, which is right while only the camera moves.  With `gb.prevTris` the point is taken where
+// it was at the last render: the same barycentrics on the triangle's previous vertices, in fetchSurface's expression operand
+// for operand, so that unmoved vertices give isec.pos bit for bit.  A kernel argument, hence a scalar branch.
+RD_DEV int gbufMotionIndex(const DCamera &cam, const DCamera &lastCam, const GBufPtrs &gb, const Surface &isec, v2 bary) {
+    v3 pLast = isec.pos;
+    if (gb.prevTris) {
+        TriVerts t = loadTri(gb.prevTris, isec.primId);
+        float w = 1.f - bary.x - bary.y;
+        pLast = t.b * bary.x + t.c * bary.y + t.a * w;
+    }
+    v2 ndc = cameraRasterUV(lastCam, pLast);  // Camera::getRasterCoord (sceneStructs.h:45-48)
+    int lx = (int)(float(lastCam.resx) * ndc.x), ly = (int)(float(lastCam.resy) * ndc.y);
+    return (lx >= 0 && lx < gb.width && ly >= 0 && ly < gb.height) ? ly * cam.resx + lx : -1;
+}
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_gbuffer(DScene s, DCamera cam, DCamera lastCam, PixelMap pm, GBufPtrs gb) {
     Pix px = mapWavePixel(pm);  // single-wave workgroups: 64 threads, one 8x8 block each
@@ -309,6 +325,7 @@ __global__ __launch_bounds__(256) void k_gbuffer(DScene s, DCamera cam, DCamera 
             nHits++;
             Surface isec;
             fetchSurface(s, h.prim, h.bary, isec);
+            gb.motion[idx] = gbufMotionIndex(cam, lastCam, gb, isec, h.bary);  // first: see gbufStore (kernels_persist.h)
             int matId = isec.matId;
             if (loadMaterial(s.mats, isec.matId).type == Light) matId = -2;  // NullPrimitive - 1 (:33-37, untextured record)
             Material material = texturedMaterial(s, isec);            // :44 (may perturb isec.norm)
@@ -316,9 +333,6 @@ __global__ __launch_bounds__(256) void k_gbuffer(DScene s, DCamera cam, DCamera 
             store3(gb.normal, idx, isec.norm);
             gb.primId[idx] = matId;
             gb.depth[idx] = length(ray.o - isec.pos);  // glm::distance(pos, origin) = length(origin - pos)
-            v2 ndc = cameraRasterUV(lastCam, isec.pos);  // Camera::getRasterCoord (sceneStructs.h:45-48)
-            int lx = (int)(float(lastCam.resx) * ndc.x), ly = (int)(float(lastCam.resy) * ndc.y);
-            gb.motion[idx] = (lx >= 0 && lx < gb.width && ly >= 0 && ly < gb.height) ? ly * cam.resx + lx : -1;
         } else {
             store3(gb.albedo, idx, hasEnvMap(s) ? envLookup(s, ray.d) : mk3(0.f));  // :61-66
             store3(gb.normal, idx, mk3(0.f));

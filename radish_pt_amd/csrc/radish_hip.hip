@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -154,6 +155,10 @@ struct rdh_ctx {
     int refitCap = 0;
     bool planValid = false;  // built by the first refit after an upload / update_geometry; dropped by those and rdh_scene_free
     bool treeRefit = false;  // the pending tree header (treePending) is a refit's: only the root box changes
+
+    // rdh_scene_track_motion: the triangle records as this context's most recent rdh_gbuffer_render saw them (scene allocation)
+    TriRec *prevTris = nullptr;
+    bool movedSinceRender = false;  // prevTris holds positions that differ from ds.tris; set by the first update after a render
 };
 
 namespace {
@@ -767,6 +772,8 @@ int rdh_scene_free(rdh_ctx *c) {
     c->dLightPrims = nullptr;
     c->updPairs = nullptr;
     c->numLights = 0;
+    c->prevTris = nullptr;  // tracking ends with the scene (its buffer was one of sceneAllocs)
+    c->movedSinceRender = false;
     return RDH_OK;
 }
 
@@ -1211,9 +1218,18 @@ int rdh_path_trace_direct(rdh_ctx *c, float *d_direct, int iter, int looper, uin
     return timeEnd(c, "pathTraceDirect");
 }
 
+static int enqueueGBuffer(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags);
+
 int rdh_gbuffer_render(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
     int rc = requireReady(c);
     if (rc) return rc;
+    if ((rc = enqueueGBuffer(c, gb, flags))) return rc;
+    c->movedSinceRender = false;  // rdh_scene_track_motion: "previous" is from now on what this render saw
+    return RDH_OK;
+}
+
+static int enqueueGBuffer(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
+    int rc;
     if (!gb || !gb->albedo || !gb->motion || (gb->frameIdx & ~1)) return fail(c, RDH_ERR_ARGS, "rdh_gbuffer_render: bad G-buffer");
     for (int k = 0; k < 2; k++)
         if (!gb->normal[k] || !gb->depth[k] || !gb->primId[k]) return fail(c, RDH_ERR_ARGS, "rdh_gbuffer_render: null plane");
@@ -1236,7 +1252,7 @@ int rdh_gbuffer_render(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
     }
     DCamera last = toDeviceCamera(gb->lastCam);
     GBufPtrs p{gb->albedo, gb->normal[gb->frameIdx], gb->motion, gb->depth[gb->frameIdx], gb->primId[gb->frameIdx],
-               gb->width, gb->height};
+               gb->width, gb->height, c->movedSinceRender ? c->prevTris : nullptr};
     if (flags & RDH_PT_ONE_LANE_PER_PIXEL) {  // one lane per pixel for the whole launch (the reference's structure)
         timeBegin(c);
         if (flags & RDH_PT_COUNT)
@@ -2557,9 +2573,15 @@ int waitSideStreams(rdh_ctx *c) {
 int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
     const int N = c->ds.numPrims;
     const int geomN = std::max(N, c->numLights);
+    // rdh_scene_track_motion: the first update since the last G-buffer render keeps what that render saw; a later one must not
+    TriRec *keep = nullptr;
+    if (c->prevTris && !c->movedSinceRender) {
+        keep = c->prevTris;
+        c->movedSinceRender = true;
+    }
     hipLaunchKernelGGL(k_geom_update, dim3((unsigned)((geomN + 255) / 256)), dim3(256), 0, c->stream, d_vertices, d_normals,
                        const_cast<TriRec *>(c->ds.tris), const_cast<AttrRec *>(c->ds.attrs), N, const_cast<LightRec *>(c->ds.lights),
-                       (const int *)c->dLightPrims, c->numLights);
+                       (const int *)c->dLightPrims, c->numLights, keep);
     if (lights && lights->lightSamplerLength > 0) {  // the caller's table goes through a pinned staging buffer: no host wait
         const int s = c->aliasStageNext, len = lights->lightSamplerLength;
         c->aliasStageNext ^= 1;
@@ -2809,6 +2831,27 @@ int rdh_scene_refit_geometry(rdh_ctx *c, const float *d_vertices, const float *d
     c->treePending = true;
     c->treeRefit = true;
     c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
+    return RDH_OK;
+}
+
+int rdh_scene_track_motion(rdh_ctx *c, int enable) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_track_motion: no scene uploaded");
+    if ((enable != 0) == (c->prevTris != nullptr)) return RDH_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (enable) {  // "previous == current": nothing to copy, the first update after this fills the buffer before any kernel reads it
+        void *p = nullptr;
+        HIP_TRY(c, hipMalloc(&p, sizeof(TriRec) * (size_t)c->ds.numPrims));
+        c->sceneAllocs.push_back(p);
+        c->prevTris = static_cast<TriRec *>(p);
+    } else {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));  // a G-buffer render may still read the buffer (switching off is not a per-frame call)
+        void *p = c->prevTris;
+        c->sceneAllocs.erase(std::find(c->sceneAllocs.begin(), c->sceneAllocs.end(), p));
+        HIP_TRY(c, hipFree(p));
+        c->prevTris = nullptr;
+    }
+    c->movedSinceRender = false;
     return RDH_OK;
 }
 

@@ -1,0 +1,191 @@
+"""numpy float32 restatement of the G-buffer's motion plane (rdh_gbuffer_render with rdh_scene_track_motion), shared
+by test_motion_model_cpu.py and test_gpu_motion.py.
+
+Operation for operation what the kernels do: gbufPrimaryRay (kernels_persist.h), the position interpolation of fetchSurface
+(lights.h), cameraRasterUV (bsdf.h) and the index rule of gbufMotionIndex (kernels_pt.h).  numpy's float32 add / sub / mul / div /
+sqrt are IEEE binary32 operations and are never contracted, which is the library's numerics contract.  The one libm
+call is the host's tanf in toDeviceCamera (radish_hip.hip); it is taken from the same libm, since np.tan need not round alike.
+
+Which triangle a pixel sees, and where, comes from the oracle's closest-hit trace of the CURRENT geometry; the model only says
+where that surface point was on the PREVIOUS vertices and which pixel of the last camera saw it there."""
+import ctypes
+import ctypes.util
+
+import numpy as np
+
+F = np.float32
+_libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+_libm.tanf.restype = ctypes.c_float
+_libm.tanf.argtypes = [ctypes.c_float]
+
+
+def _v(a):
+    return [F(x) for x in np.asarray(a, np.float32).reshape(-1)]
+
+
+def device_camera(cam):
+    """toDeviceCamera: the fields the kernels use, tanFovY recomputed with libm's tanf of (degrees * pi/180) in float32."""
+    cam = np.asarray(cam)
+    m = _v(cam["rotationMatInv"])
+    return {
+        "resx": int(cam["resolution"][0]), "resy": int(cam["resolution"][1]),
+        "position": _v(cam["position"]), "view": _v(cam["view"]), "up": _v(cam["up"]), "right": _v(cam["right"]),
+        "inv": (m[0:3], m[3:6], m[6:9]),  # columns, as glm::mat3
+        "focalDist": F(cam["focalDist"]),
+        "tanFovY": F(_libm.tanf(ctypes.c_float(F(cam["fov"][1]) * F(0.01745329251994329576923690768489)))),
+    }
+
+
+# ---- rmath.h on component arrays: a vector is a list of three float32 arrays ----
+def _dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _mul(cols, v):  # glm mat3 * vec3, columns c0 c1 c2
+    c0, c1, c2 = cols
+    return [(c0[k] * v[0] + c1[k] * v[1]) + c2[k] * v[2] for k in range(3)]
+
+
+def _normalize(v):
+    r = F(1) / np.sqrt(_dot(v, v))
+    return [v[0] * r, v[1] * r, v[2] * r]
+
+
+def primary_rays(cam):
+    """gbufPrimaryRay for every pixel in frame order: (origin [3] float32, directions [n, 3] float32)."""
+    c = device_camera(cam)
+    W, H = c["resx"], c["resy"]
+    with np.errstate(all="ignore"):
+        idx = np.arange(W * H)
+        x, y = (idx % W).astype(F), (idx // W).astype(F)
+        aspect = F(W) / F(H)
+        px, py = F(1) / F(W), F(1) / F(H)
+        ru = (x * px) + px * F(0.5)
+        rv = (y * py) + py * F(0.5)
+        ru = F(1) - ru * F(2)
+        rv = F(1) - rv * F(2)
+        fx = (ru * aspect) * c["tanFovY"]
+        fy = (rv * F(1)) * c["tanFovY"]
+        pf = [fx * c["focalDist"], fy * c["focalDist"], np.full_like(fx, F(1) * c["focalDist"])]
+        d = [pf[0] - F(0), pf[1] - F(0), pf[2] - F(0)]  # pFocus - pLens, pLens = 0
+        d = _normalize(_mul((c["right"], c["up"], c["view"]), d))
+        o = [(c["position"][k] + c["right"][k] * F(0)) + c["up"][k] * F(0) for k in range(3)]
+    return np.array(o, F), np.stack(d, axis=1).astype(F)
+
+
+def interpolate(verts, prim, u, v):
+    """fetchSurface's position: t.b * bary.x + t.c * bary.y + t.a * (1 - bary.x - bary.y), per component."""
+    t = np.ascontiguousarray(verts, F).reshape(-1, 3, 3)[prim]
+    w = (F(1) - u) - v
+    return [(t[:, 1, k] * u + t[:, 2, k] * v) + t[:, 0, k] * w for k in range(3)]
+
+
+def raster_index(last_cam, pos, width, height, stride):
+    """cameraRasterUV into `last_cam` and gbufMotionIndex's rule: ly * stride + lx, or -1 outside the G-buffer."""
+    c = device_camera(last_cam)
+    with np.errstate(all="ignore"):
+        dirv = _normalize([pos[k] - c["position"][k] for k in range(3)])
+        d = F(1) / _dot(dirv, c["view"])
+        p = _mul(c["inv"], [dirv[0] * d, dirv[1] * d, dirv[2] * d])
+        aspect = F(c["resx"]) / F(c["resy"])
+        sx, sy = aspect * c["tanFovY"], F(1) * c["tanFovY"]
+        p = [p[0] / sx, p[1] / sy, p[2] / F(1)]
+        ux = (-p[0]) * F(0.5) + F(0.5)
+        uy = (-p[1]) * F(0.5) + F(0.5)
+        fx, fy = F(c["resx"]) * ux, F(c["resy"]) * uy
+
+    def to_int(f):  # the device's float -> int conversion: towards zero, saturating, NaN -> 0
+        f = np.where(np.isnan(f), F(0), f).astype(np.float64)
+        return np.clip(np.trunc(f), -2147483648.0, 2147483647.0).astype(np.int64)
+
+    lx, ly = to_int(fx), to_int(fy)
+    inside = (lx >= 0) & (lx < width) & (ly >= 0) & (ly < height)
+    return np.where(inside, ly * stride + lx, -1).astype(np.int32)
+
+
+def trace(oracle_cur, cam):
+    """The centre rays of `cam` and the oracle's closest hits on them: (origin, directions, hits)."""
+    o, d = primary_rays(cam)
+    rays = np.concatenate([np.broadcast_to(o, d.shape), d], axis=1).astype(F)
+    return o, d, oracle_cur.trace_closest(rays)
+
+
+def motion_plane(oracle_cur, verts_cur, verts_prev, cam, last_cam, hits=None):
+    """The motion plane of a tracked render: per pixel of `cam`, the pixel of `last_cam` that saw the hit point where it was on
+    `verts_prev` (-1: outside last frame; 0 on a miss).  `oracle_cur` holds the current geometry."""
+    if hits is None:
+        hits = trace(oracle_cur, cam)[2]
+    W, H = int(cam["resolution"][0]), int(cam["resolution"][1])
+    hit = hits["primId"] >= 0
+    prim = np.where(hit, hits["primId"], 0)
+    with np.errstate(all="ignore"):
+        pos = interpolate(verts_prev, prim, hits["u"], hits["v"])
+    idx = raster_index(last_cam, pos, W, H, W)
+    return np.where(hit, idx, 0).astype(np.int32)
+
+
+def depth_plane(oracle_cur, verts_cur, cam, hits=None):
+    """length(ray.o - pos) on hits, 1 on misses: the G-buffer's depth plane, which pins the ray and the interpolation."""
+    o, _, h = trace(oracle_cur, cam) if hits is None else (primary_rays(cam)[0], None, hits)
+    hit = h["primId"] >= 0
+    with np.errstate(all="ignore"):
+        pos = interpolate(verts_cur, np.where(hit, h["primId"], 0), h["u"], h["v"])
+        dv = [o[k] - pos[k] for k in range(3)]
+        depth = np.sqrt(_dot(dv, dv))
+    return np.where(hit, depth, F(1)).astype(F)
+
+
+# ---- the moving test scene shared by the CPU and GPU tests ----
+MOVED_MATERIAL = 6  # cornell's dielectric stand-in: in front of the others, and under the centre column of an axis-aligned camera
+
+
+def deformed(sd, step, material=MOVED_MATERIAL):
+    """`sd` with the triangles of one material (MOVED_MATERIAL by default) moved: a translation of `step` times
+    (0.1, 0.03, 0.05) plus a twist about the object's vertical axis that grows with height, so that no two vertices at different
+    heights move alike.  Step 0 is `sd`'s own geometry.  Normals turn with their vertices."""
+    from radish_pt_amd import scenes
+
+    sel = sd.material_ids == material
+    assert sel.any(), f"no triangle of material {material}"
+    if step == 0:  # the uploaded arrays themselves, not their image under a float64 round trip
+        return scenes.SceneData(f"{sd.name}_step0", sd.vertices, sd.normals, sd.texcoords, sd.material_ids, sd.materials, sd.textures,
+                                sd.env_map_tex_id)
+    v = sd.vertices.reshape(-1, 3, 3).astype(np.float64)
+    n = sd.normals.reshape(-1, 3, 3).astype(np.float64)
+    p, q = v[sel], n[sel]
+    ctr = p.reshape(-1, 3).mean(axis=0)
+    ang = step * (0.2 + 1.5 * (p[..., 1] - p[..., 1].min()))
+    c, s = np.cos(ang), np.sin(ang)
+    dx, dz = p[..., 0] - ctr[0], p[..., 2] - ctr[2]
+    out = p.copy()
+    out[..., 0] = ctr[0] + c * dx + s * dz + 0.1 * step
+    out[..., 1] = p[..., 1] + 0.03 * step
+    out[..., 2] = ctr[2] - s * dx + c * dz + 0.05 * step
+    qn = q.copy()
+    qn[..., 0] = c * q[..., 0] + s * q[..., 2]
+    qn[..., 2] = -s * q[..., 0] + c * q[..., 2]
+    v[sel], n[sel] = out, qn
+    return scenes.SceneData(f"{sd.name}_step{step}", v.astype(F).reshape(-1, 3), n.astype(F).reshape(-1, 3), sd.texcoords,
+                            sd.material_ids, sd.materials, sd.textures, sd.env_map_tex_id)
+
+
+def moving_cameras(width, height, frames=3, literal=False):
+    """A camera that moves every frame.  literal: the axis-aligned camera whose centre row and column are literal-class rays
+    (odd sizes), as in test_gbuffer_literal_rays_bit_exact; it moves along y only, so it stays axis-aligned, and it
+    sees the whole room from afar (the room fills a third of the frame's height)."""
+    from radish_pt_amd import hostlib
+
+    if literal:
+        return [hostlib.make_camera(width, height, eye=(0.0, 1.0 + 0.5 * f, 9.0), rotation=(-90.0, 0.0, 0.0), fovy=19.0) for f in range(frames)]
+    return [hostlib.make_camera(width, height, eye=(0.05 * f, 1.0 + 0.02 * f, 4.2), rotation=(-90.0 + 0.7 * f, 0.4 * f, 0.0), fovy=20.0)
+            for f in range(frames)]
+
+
+def passes_temporal_test(idx, prim_cur, prim_last, normal_cur, normal_last):
+    """findTemporalNeighbor's acceptance (kernels_restir.h) per pixel: the index names a pixel of last frame, this pixel's id is a
+    surface's and equals last frame's id there, and the two normals are not near-perpendicular."""
+    ok = (idx >= 0) & (prim_cur >= 0)
+    j = np.where(idx >= 0, idx, 0)
+    ok &= prim_last[j] == prim_cur
+    nn = np.abs((normal_cur.astype(np.float64) * normal_last[j].astype(np.float64)).sum(axis=1))
+    return ok & (nn >= 0.1)
