@@ -223,6 +223,32 @@ int rdh_scene_track_motion(rdh_ctx *ctx, int enable);
  * 1 the sibling pairs ((bvhSize - 1) / 2 + 1 records of 64 B; 0 bytes when the scene has none), 2 {int32 treeDepth, hasPairs, 0, 0;
  * float rootLo[4]; float rootHi[4]} (48 B).  Returns the byte size (hostOut NULL: only that) or a negative RDH_ERR_*.  Blocking. */
 long long rdh_debug_read_tree(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
+/* ---- the light sampler of moving emissive geometry ------------------------------------------------------------------
+ * The update and refit entries rewrite the emissive triangles' records; the alias table over their powers and sumLightPowerInv
+ * either come with the call (rdh_light_update, built on the host) or are rebuilt here from the records the scene holds.
+ * rdh_build_alias_table_device: the device twin of rdh_build_alias_table (include/radish_host.h) — d_values float[n] -> d_table
+ * {float prob; int32 failId}[n] and *d_sum (the strictly sequential binary32 sum of the values), bit for bit what the host function
+ * writes, NaN payloads aside (a sum of zero gives {NaN, i} entries as on the host).  Device pointers; asynchronous on the context's
+ * stream; needs no scene; its scratch grows with n (growing it waits for the stream).  n == 0: RDH_OK, nothing written; n < 0 or a
+ * null pointer with n > 0: RDH_ERR_ARGS.
+ * rdh_scene_rebuild_lights: the light powers rdh_build_light_list computes, from the scene's CURRENT emissive-triangle records (as
+ * the upload or the last update / refit left them; with an environment map the last entry is envPower, the environment's total
+ * power as passed to rdh_build_alias_table when the scene was made) -> the scene's alias table, sumLightPowerInv = 1.f / sum and
+ * the per-light constants again.  A scene whose lights were rebuilt so renders bit for bit like a fresh upload of the moved scene.
+ * Asynchronous on the context's stream: sumLightPowerInv reaches the host the way an update's tree header does, and the next render
+ * call waits for it before it launches.  Call it after an update or refit that was given lights = NULL, or at any other time; a
+ * later update that brings a rdh_light_update replaces what a rebuild still in flight computes.  Scratch is allocated by the first
+ * rebuild of a scene, sized by lightSamplerLength.  ReSTIR reservoirs are kept.  No scene, or (on a scene with an environment map)
+ * an envPower that is negative or not finite: RDH_ERR_ARGS, the scene unchanged and nothing enqueued.  Without an environment map
+ * envPower is ignored; lightSamplerLength == 0: RDH_OK, nothing done.
+ * rdh_debug_read_lights: test access to the light sampler the kernels read: which = 0 the alias table (lightSamplerLength x 8 B),
+ * 1 {float sum, sumLightPowerInv; int32 lightSamplerLength, numLights} (16 B; sum is 1.f / sumLightPowerInv, the reciprocal of the
+ * frame kernels' argument as it stands: an upload brings only that value), 2 the per-light constants (numLights x 64 B: the
+ * emissive triangle's record, its normal and power * sumLightPowerInv).  Returns the byte size (hostOut NULL: only that) or a
+ * negative RDH_ERR_*.  Blocking; folds a rebuild still in flight in first, like rdh_debug_read_tree. */
+int rdh_build_alias_table_device(rdh_ctx *ctx, const float *d_values, int32_t n, void *d_table, float *d_sum);
+int rdh_scene_rebuild_lights(rdh_ctx *ctx, float envPower);
+long long rdh_debug_read_lights(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
 /* Replaces DevScene::destroy (src/scene.cpp:553-574). */
 int rdh_scene_free(rdh_ctx *ctx);
 /* The `Camera cam` kernel argument of every reference kernel (State::scene->camera, src/pathtrace.cu:356). */

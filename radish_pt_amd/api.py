@@ -62,6 +62,7 @@ EXPORTS = [
     "rdh_scene_refit_geometry", "rdh_scene_tree_cost",
     "rdh_build_bvh_device_ex", "rdh_scene_update_geometry_ex",
     "rdh_scene_track_motion",
+    "rdh_build_alias_table_device", "rdh_scene_rebuild_lights", "rdh_debug_read_lights",
 ]
 
 
@@ -187,6 +188,9 @@ def lib():
             "rdh_build_bvh_device_ex": ([vp, vp, i32, i32, vp, C.POINTER(vp)], i32),
             "rdh_scene_update_geometry_ex": ([vp, vp, vp, C.POINTER(LightUpdateC), i32], i32),
             "rdh_scene_track_motion": ([vp, i32], i32),
+            "rdh_build_alias_table_device": ([vp, vp, i32, vp, vp], i32),
+            "rdh_scene_rebuild_lights": ([vp, C.c_float], i32),
+            "rdh_debug_read_lights": ([vp, i32, vp, i64], i64),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -379,6 +383,40 @@ class Context:
             if rc < 0:
                 self.check(int(rc))
         return out
+
+    # ---- moving geometry: the light sampler ----
+    def build_alias_table_device(self, values):
+        """values: float32 cuda tensor [n] -> (table int32 [n, 2], sum float32 [1]) on the device: row i of table is
+        layouts.BINOMIAL_DTYPE's {prob (its bits), failId}, bit for bit hostlib.build_alias_table of the same values
+        (rdh_build_alias_table_device).  Asynchronous on the context's stream."""
+        torch = _torch()
+        if not isinstance(values, torch.Tensor) or values.dim() != 1:
+            raise RadishError("build_alias_table_device: values must be a one-dimensional tensor")
+        n = values.numel()
+        vp = self._ptr(values, n, "build_alias_table_device values")
+        table = torch.empty(n, 2, dtype=torch.int32, device=values.device)
+        total = torch.zeros(1, dtype=torch.float32, device=values.device)
+        self.check(lib().rdh_build_alias_table_device(self.h, vp, n, table.data_ptr(), total.data_ptr()))
+        return table, total
+
+    def rebuild_lights(self, env_power=0.0):
+        """The uploaded scene's alias table, sumLightPowerInv and per-light constants again, from the emissive triangles as the last
+        update_geometry / refit_geometry left them (rdh_scene_rebuild_lights).  env_power: SceneData.env_power of a scene with an
+        environment map (ignored without one).  Does not block."""
+        self.check(lib().rdh_scene_rebuild_lights(self.h, float(env_power)))
+
+    def debug_read_lights(self, which):
+        """Blocking test access (rdh_debug_read_lights): 0 -> the alias table (layouts.BINOMIAL_DTYPE), 1 -> {float32 sum,
+        sumLightPowerInv; int32 lightSamplerLength, numLights} as 16 bytes, 2 -> the LightPre records' bytes."""
+        n = lib().rdh_debug_read_lights(self.h, which, None, 0)
+        if n < 0:
+            self.check(int(n))
+        out = np.zeros(n, np.uint8)
+        if n:
+            rc = lib().rdh_debug_read_lights(self.h, which, out.ctypes.data, n)
+            if rc < 0:
+                self.check(int(rc))
+        return out.view(L.BINOMIAL_DTYPE) if which == 0 else out
 
     def set_camera(self, cam):
         buf = np.frombuffer(np.asarray(cam, dtype=L.CAMERA_DTYPE).tobytes(), np.uint8).copy()

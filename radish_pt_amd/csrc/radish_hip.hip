@@ -10,6 +10,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -28,6 +29,7 @@
 #include "device/kernels_bvh.h"
 #include "device/kernels_refit.h"
 #include "device/kernels_lbvh.h"
+#include "device/kernels_lights.h"
 
 using namespace rd;
 
@@ -159,6 +161,14 @@ struct rdh_ctx {
     // rdh_scene_track_motion: the triangle records as this context's most recent rdh_gbuffer_render saw them (scene allocation)
     TriRec *prevTris = nullptr;
     bool movedSinceRender = false;  // prevTris holds positions that differ from ds.tris; set by the first update after a render
+
+    // rdh_scene_rebuild_lights / rdh_build_alias_table_device (kernels_lights.h)
+    void *lightScratch = nullptr;    // powers + AliasWork for the scene's lightSamplerLength (scene allocation, made by the first rebuild)
+    void *aliasScratch = nullptr;    // AliasWork of rdh_build_alias_table_device for aliasCap values
+    int aliasCap = 0;
+    float *hLightSums = nullptr;     // pinned copy of a rebuild's {sum, 1 / sum}
+    hipEvent_t evLights = nullptr;   // recorded after that copy
+    bool lightsPending = false;      // a rebuild's sumLightPowerInv has not been folded into ds yet (settleLights)
 };
 
 namespace {
@@ -410,11 +420,23 @@ int settleTree(rdh_ctx *c) {
     return RDH_OK;
 }
 
+// Fold the sumLightPowerInv of the last rdh_scene_rebuild_lights into ds (a by-value argument of every frame kernel), the way
+// settleTree folds the tree header: waits for that rebuild, which the stream has to finish before the next launch anyway.  A later
+// update that brought a host rdh_light_update has cleared lightsPending: its value stands.
+int settleLights(rdh_ctx *c) {
+    if (!c->lightsPending) return RDH_OK;
+    HIP_TRY(c, hipEventSynchronize(c->evLights));
+    c->lightsPending = false;
+    c->ds.sumLightPowerInv = c->hLightSums[1];
+    return RDH_OK;
+}
+
 int requireReady(rdh_ctx *c) {
     if (!c) return RDH_ERR_ARGS;
     if (c->haveScene) {
         int rc = settleTree(c);
         if (rc) return rc;
+        if ((rc = settleLights(c))) return rc;
     }
     if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded (rdh_scene_upload)");
     if (!c->haveCamera) return fail(c, RDH_ERR_NO_SCENE, "no camera set (rdh_set_camera)");
@@ -769,6 +791,8 @@ int rdh_scene_free(rdh_ctx *c) {
     c->treePending = false;
     c->treeRefit = false;
     c->planValid = false;
+    c->lightsPending = false;
+    c->lightScratch = nullptr;  // one of sceneAllocs
     c->dLightPrims = nullptr;
     c->updPairs = nullptr;
     c->numLights = 0;
@@ -799,6 +823,9 @@ void rdh_destroy(rdh_ctx *c) {
     if (c->hTreeHdr) hipHostFree(c->hTreeHdr);
     if (c->evTree) hipEventDestroy(c->evTree);
     if (c->evUpdWait) hipEventDestroy(c->evUpdWait);
+    if (c->aliasScratch) hipFree(c->aliasScratch);
+    if (c->hLightSums) hipHostFree(c->hLightSums);
+    if (c->evLights) hipEventDestroy(c->evLights);
     for (int k = 0; k < 2; k++) {
         if (c->hAliasStage[k]) hipHostFree(c->hAliasStage[k]);
         if (c->evAliasStage[k]) hipEventDestroy(c->evAliasStage[k]);
@@ -2531,6 +2558,18 @@ int launchLbvhBuild(rdh_ctx *c, LbvhWork &L, BvhWork &w) {
     return RDH_OK;
 }
 
+// The workspace of the alias-table kernels for n values, carved from one allocation of aliasWorkBytes(n): the powers first.
+size_t aliasWorkBytes(int n) { return alignUp(sizeof(float) * (size_t)n) + 2 * alignUp(sizeof(int2) * (size_t)n) + 256; }
+AliasWork lightWork(void *buf, int n) {
+    char *p = static_cast<char *>(buf) + alignUp(sizeof(float) * (size_t)n);
+    AliasWork w{};
+    w.over = reinterpret_cast<int2 *>(p);
+    w.under = reinterpret_cast<int2 *>(p + alignUp(sizeof(int2) * (size_t)n));
+    w.sums = reinterpret_cast<float *>(p + 2 * alignUp(sizeof(int2) * (size_t)n));
+    w.counts = reinterpret_cast<int *>(w.sums + 2);
+    return w;
+}
+
 // Shared by rdh_scene_update_geometry and rdh_scene_refit_geometry.
 int checkGeomArgs(rdh_ctx *c, const char *what, const float *d_vertices, const rdh_light_update *lights) {
     if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "%s: no scene uploaded", what);
@@ -2598,10 +2637,19 @@ int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals,
                                   c->stream));
         HIP_TRY(c, hipEventRecord(c->evAliasStage[s], c->stream));
     }
-    if (lights) c->ds.sumLightPowerInv = lights->sumLightPowerInv;
-    if (c->numLights > 0)
-        hipLaunchKernelGGL(k_light_precompute, dim3((unsigned)((c->numLights + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights,
-                           const_cast<LightPre *>(c->ds.lightPre), c->numLights, c->ds.sumLightPowerInv);
+    if (lights) {
+        c->ds.sumLightPowerInv = lights->sumLightPowerInv;
+        c->lightsPending = false;  // the caller's table and value replace those of a rebuild enqueued before this update
+    }
+    if (c->numLights > 0) {
+        const dim3 grid((unsigned)((c->numLights + 255) / 256));
+        if (c->lightsPending)  // a rebuild's value, not on the host yet: read it where the rebuild left it
+            hipLaunchKernelGGL(k_light_precompute_dev, grid, dim3(256), 0, c->stream, c->ds.lights, const_cast<LightPre *>(c->ds.lightPre),
+                               c->numLights, (const float *)lightWork(c->lightScratch, c->ds.lightSamplerLength).sums + 1);
+        else
+            hipLaunchKernelGGL(k_light_precompute, grid, dim3(256), 0, c->stream, c->ds.lights, const_cast<LightPre *>(c->ds.lightPre),
+                               c->numLights, c->ds.sumLightPowerInv);
+    }
     return RDH_OK;
 }
 
@@ -2894,6 +2942,103 @@ long long rdh_debug_read_tree(rdh_ctx *c, int which, void *hostOut, long long ma
         memcpy(hostOut, h, 16);
         memcpy(static_cast<char *>(hostOut) + 16, &c->ds.rootLo, 16);
         memcpy(static_cast<char *>(hostOut) + 32, &c->ds.rootHi, 16);
+    }
+    return bytes;
+}
+
+}  // extern "C"
+
+// ---- the light sampler on the device (kernels_lights.h) ---------------------------------------------------------------------------
+namespace {
+
+// values -> table, w.sums, on the context's stream.
+void launchAliasBuild(rdh_ctx *c, const float *d_values, int n, const AliasWork &w, AliasRec *d_table) {
+    hipLaunchKernelGGL(k_alias_classify, dim3(1), dim3(64), 0, c->stream, d_values, n, w);
+    hipLaunchKernelGGL(k_alias_sweep, dim3(1), dim3(64), 0, c->stream, w, d_table);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_build_alias_table_device(rdh_ctx *c, const float *d_values, int32_t n, void *d_table, float *d_sum) {
+    if (!c) return RDH_ERR_ARGS;
+    if (n < 0 || (n > 0 && (!d_values || !d_table || !d_sum)))
+        return fail(c, RDH_ERR_ARGS, "rdh_build_alias_table_device: bad arguments");
+    if (n == 0) return RDH_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n > c->aliasCap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->aliasScratch) hipFree(c->aliasScratch);
+        c->aliasScratch = nullptr;
+        c->aliasCap = 0;
+        HIP_TRY(c, hipMalloc(&c->aliasScratch, aliasWorkBytes(n)));
+        c->aliasCap = n;
+    }
+    const AliasWork w = lightWork(c->aliasScratch, c->aliasCap);
+    launchAliasBuild(c, d_values, n, w, static_cast<AliasRec *>(d_table));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(d_sum, w.sums, sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    return RDH_OK;
+}
+
+int rdh_scene_rebuild_lights(rdh_ctx *c, float envPower) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "rdh_scene_rebuild_lights: no scene uploaded");
+    const bool hasEnv = c->ds.envTex >= 0;
+    if (hasEnv && !(envPower >= 0.f && envPower <= FLT_MAX))
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_rebuild_lights: envPower %g must be finite and not negative", (double)envPower);
+    const int len = c->ds.lightSamplerLength;
+    if (len == 0) return RDH_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensureTreeHeader(c);
+    if (rc) return rc;
+    if (!c->evLights) {
+        HIP_TRY(c, hipHostMalloc((void **)&c->hLightSums, 2 * sizeof(float), hipHostMallocDefault));
+        HIP_TRY(c, hipEventCreateWithFlags(&c->evLights, hipEventDisableTiming));
+    }
+    if (!c->lightScratch) {
+        void *p = nullptr;
+        HIP_TRY(c, hipMalloc(&p, aliasWorkBytes(len)));
+        c->sceneAllocs.push_back(p);
+        c->lightScratch = p;
+    }
+    if ((rc = waitSideStreams(c))) return rc;  // the table and the per-light constants are rewritten in place
+    float *power = static_cast<float *>(c->lightScratch);
+    const AliasWork w = lightWork(c->lightScratch, len);
+    hipLaunchKernelGGL(k_light_power, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights, c->numLights, len,
+                       envPower, power);
+    launchAliasBuild(c, power, len, w, const_cast<AliasRec *>(c->ds.lightAlias));
+    if (c->numLights > 0)
+        hipLaunchKernelGGL(k_light_precompute_dev, dim3((unsigned)((c->numLights + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights,
+                           const_cast<LightPre *>(c->ds.lightPre), c->numLights, (const float *)w.sums + 1);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->hLightSums, w.sums, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evLights, c->stream));
+    c->lightsPending = true;
+    return RDH_OK;
+}
+
+long long rdh_debug_read_lights(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (int rc = settleLights(c)) return rc;
+    long long bytes;
+    if (which == 0) bytes = (long long)sizeof(AliasRec) * c->ds.lightSamplerLength;
+    else if (which == 1) bytes = 16;
+    else if (which == 2) bytes = (long long)sizeof(LightPre) * c->numLights;
+    else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lights: which = %d", which);
+    if (!hostOut) return bytes;
+    if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lights: %lld bytes needed", bytes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (which == 0 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.lightAlias, bytes, hipMemcpyDeviceToHost));
+    else if (which == 2 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.lightPre, bytes, hipMemcpyDeviceToHost));
+    else if (which == 1) {
+        const float f[2] = {1.f / c->ds.sumLightPowerInv, c->ds.sumLightPowerInv};
+        const int32_t n[2] = {c->ds.lightSamplerLength, c->numLights};
+        memcpy(hostOut, f, 8);
+        memcpy(static_cast<char *>(hostOut) + 8, n, 8);
     }
     return bytes;
 }

@@ -69,9 +69,11 @@ class SceneData:
         )
         self.num_lights = len(self.light_prim_ids)
         power = self.light_power
+        self.env_power = np.float32(0.0)  # the environment entry's power (Context.rebuild_lights' argument); 0.0 without an env map
         if self.env_map_tex_id >= 0:  # Scene::createLightSampler: the env map is the LAST light entry (src/scene.cpp:146-164)
             env = self.textures[self.env_map_tex_id]
             self.env_map_sampler, env_sum = hostlib.build_envmap_sampler(env, env.shape[1], env.shape[0])
+            self.env_power = np.float32(env_sum)
             power = np.concatenate([power, np.array([env_sum], np.float32)]).astype(np.float32)
         else:
             self.env_map_sampler = np.zeros(0, dtype=L.BINOMIAL_DTYPE)
