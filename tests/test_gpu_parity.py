@@ -307,6 +307,75 @@ def test_path_trace_direct_bit_exact(cornell_gpu, cornell_small):
     assert ref.max() > 0
 
 
+def test_occupancy_share_changes_no_result(cornell_gpu, cornell_small):
+    """rdh_set_occupancy_share divides the persistent grids between contexts that render side by side; how many workgroups take
+    the work must not show in any result.  128x96 is the smallest frame at which the largest share (64) bites: 192 blocks of path
+    tracing and 192 chunks of rays against the 48 and 112 workgroups that a 64th of the resident grids leaves (at 64x48 the work
+    is the smaller number).  Every entry whose grid is sized by the share, at share 64, equals itself at share 1 bit for bit, and
+    the path traces equal the oracle."""
+    from radish_pt_amd import api, layouts as L, scenes
+
+    torch = _torch()
+    ctx = cornell_gpu
+    W, H, depth, looper = 128, 96, 4, 21
+    n = W * H
+    cam = scenes.cornell_camera(W, H)
+    ctx.set_camera(cam)
+    ref_d = np.zeros((n, 3), np.float32)
+    ref_i = np.zeros((n, 3), np.float32)
+    _oracle(cornell_small).path_trace(cam, ref_d, ref_i, 0, looper, depth)
+    rays = ctx.dump_rays(looper, 0)[0].contiguous()  # depth 0: the frame's primary rays
+    assert rays.shape[0] == n
+    segs = rays.clone()  # ... and segments along them, 1 to 6 units long: the room is 3.2 to 5.2 units from the eye
+    segs[:, 3:] = rays[:, :3] + rays[:, 3:] * (1 + torch.arange(n, device="cuda") % 6)[:, None]
+    gb = api.GBuffer()
+    gb.create(W, H)
+
+    def every_entry():
+        out = {}
+        for name, flags in (("persistent", api.RDH_PT_PERSISTENT), ("wavefront_sort", api.RDH_PT_WAVEFRONT | api.RDH_PT_SORT_MATERIAL)):
+            d, i = torch.zeros(n, 3, device="cuda"), torch.zeros(n, 3, device="cuda")
+            ctx.path_trace(d, i, 0, looper, depth, flags)
+            out[f"path_trace {name} direct"], out[f"path_trace {name} indirect"] = d.cpu().numpy(), i.cpu().numpy()
+        for name, walk in (("threaded", api.RDH_PT_NO_PAIRS), ("pairs", api.RDH_PT_PAIRS)):
+            hits = torch.full((n, 4), 0x7fffffff, dtype=torch.int32, device="cuda")  # poison: an unwritten record shows
+            occ = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+            ctx.trace_closest(rays, hits, api.RDH_PT_PERSISTENT | walk)
+            ctx.trace_occluded(segs, occ, api.RDH_PT_PERSISTENT | walk)
+            out[f"trace_closest {name}"], out[f"trace_occluded {name}"] = hits.cpu().numpy(), occ.cpu().numpy()
+        img = torch.zeros(n, 3, device="cuda")
+        ctx.restir_init()
+        ctx.gbuffer_render(gb.c_struct(cam_fallback=cam))
+        ctx.restir_direct(img, 0, looper, gb.c_struct(cam), 3)
+        ctx.synchronize()
+        for plane in ("albedo", "motion"):
+            out[f"gbuffer {plane}"] = getattr(gb, plane).cpu().numpy()
+        for plane in ("normal", "depth", "primId"):
+            out[f"gbuffer {plane}"] = getattr(gb, plane)[gb.frameIdx].cpu().numpy()
+        out["restir image"] = img.cpu().numpy()
+        out["restir reservoirs"] = ctx.restir_read(1).view(np.uint8)
+        ctx.restir_free()
+        return out
+
+    alone = every_entry()
+    try:
+        ctx.set_occupancy_share(64)  # the largest the entry accepts
+        shared = every_entry()
+    finally:
+        ctx.set_occupancy_share(1)
+    assert alone.keys() == shared.keys()
+    for key, a in alone.items():
+        assert a.tobytes() == shared[key].tobytes(), key
+    for got in (alone, shared):
+        for name in ("persistent", "wavefront_sort"):
+            assert_bit_equal(got[f"path_trace {name} direct"], ref_d, f"{name} directIllum")
+            assert_bit_equal(got[f"path_trace {name} indirect"], ref_i, f"{name} indirectIllum")
+    # the runs did something: lit pixels, rays that hit, occluded and free segments, lit ReSTIR pixels
+    assert ref_d.max() > 0 and ref_i.max() > 0 and alone["restir image"].max() > 0
+    assert (alone["trace_closest pairs"].view(L.HIT_DTYPE)["primId"] >= 0).mean() > 0.3
+    assert 0 < alone["trace_occluded pairs"].mean() < 1
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # G-buffer + ReSTIR, three frames with a moving camera (temporal reuse across different motion vectors)
 # ---------------------------------------------------------------------------------------------------------------------
