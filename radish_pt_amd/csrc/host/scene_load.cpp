@@ -514,12 +514,39 @@ bool inverse4(const M4 &in, M4 &out) {  // cofactor expansion (glm::inverse's fo
     return true;
 }
 
+// X = T * R * S and its inverse from a ModelInstance's Translate / Rotate (degrees) / Scale: Math::buildTransformationMatrix
+// (mathUtil.cpp:12-25).  The one copy of this arithmetic: loadModel and rdh_object_transform both come here.  false: singular.
+bool objectTransform(const float tr[3], const float rot[3], const float sc[3], M4 &X, M4 &Xi) {
+    const float PI = 3.1415926535897932384626422832795028841971f;
+    M4 T = identity();
+    T.m[3][0] = tr[0];
+    T.m[3][1] = tr[1];
+    T.m[3][2] = tr[2];
+    M4 R = mul(mul(rotateAxis(rot[0] * PI / 180.f, 0), rotateAxis(rot[1] * PI / 180.f, 1)), rotateAxis(rot[2] * PI / 180.f, 2));
+    M4 S = identity();
+    S.m[0][0] = sc[0];
+    S.m[1][1] = sc[1];
+    S.m[2][2] = sc[2];
+    X = mul(mul(T, R), S);
+    return inverse4(X, Xi);
+}
+
+struct PooledMesh {
+    Mesh mesh;
+    int32_t restFirstPrim;  // where the mesh starts in Parsed::restVertices / restNormals
+};
+
 struct Parsed {
     std::vector<float> vertices, normals, texcoords;
     std::vector<int32_t> materialIds;
     std::vector<Material> materials;
     std::vector<Image> images;
     std::vector<rdh_host_texture> textures;
+    // rdh_scene_parse_objects: the Object blocks and the meshes they name, before the transform (object space).  Two objects
+    // that name the same OBJ share one pooled mesh and so one rest range.
+    std::map<std::string, PooledMesh> meshPool;
+    std::vector<float> restVertices, restNormals;
+    std::vector<rdh_parsed_object> objects;  // the loaded `Object` blocks, in file order
     rdh_parsed_scene pub{};
 };
 
@@ -530,7 +557,6 @@ struct Loader {
     void *user = nullptr;
     Parsed *out = nullptr;
     std::map<std::string, int> materialMap, textureMap;
-    std::map<std::string, Mesh> meshPool;
     bool flipTextures = true;
 
     std::string resolve(const std::string &p) const {  // the reference opens paths relative to its working directory;
@@ -586,13 +612,25 @@ struct Loader {
         std::string filename = line;
         while (!filename.empty() && isspace((unsigned char)filename.back())) filename.pop_back();
         const Mesh *mesh = nullptr;
+        int32_t restFirstPrim = 0;
         if (filename.find(".obj") != std::string::npos) {
-            auto it = meshPool.find(filename);
-            if (it == meshPool.end()) {
+            auto it = out->meshPool.find(filename);
+            if (it == out->meshPool.end()) {
                 std::string path = resolve(filename);
-                if (fileExists(path)) it = meshPool.emplace(filename, loadOBJ(path)).first;
+                if (fileExists(path)) {
+                    PooledMesh pm{loadOBJ(path), (int32_t)(out->restVertices.size() / 9)};
+                    for (size_t i = 0; i < pm.mesh.vertices.size(); i++) {
+                        const V3 p = pm.mesh.vertices[i], n = pm.mesh.normals[i];
+                        out->restVertices.insert(out->restVertices.end(), {p.x, p.y, p.z});
+                        out->restNormals.insert(out->restNormals.end(), {n.x, n.y, n.z});
+                    }
+                    it = out->meshPool.emplace(filename, std::move(pm)).first;
+                }
             }
-            if (it != meshPool.end()) mesh = &it->second;
+            if (it != out->meshPool.end()) {
+                mesh = &it->second.mesh;
+                restFirstPrim = it->second.restFirstPrim;
+            }
         }
         if (!mesh) {  // "[Fail to load, skipped]"
             while (!line.empty() && fp.good()) safeGetline(fp, line);
@@ -625,18 +663,15 @@ struct Loader {
             if (!fp.good()) break;
             safeGetline(fp, line);
         }
-        const float PI = 3.1415926535897932384626422832795028841971f;
-        M4 T = identity();
-        T.m[3][0] = tr[0];
-        T.m[3][1] = tr[1];
-        T.m[3][2] = tr[2];
-        M4 R = mul(mul(rotateAxis(rot[0] * PI / 180.f, 0), rotateAxis(rot[1] * PI / 180.f, 1)), rotateAxis(rot[2] * PI / 180.f, 2));
-        M4 S = identity();
-        S.m[0][0] = sc[0];
-        S.m[1][1] = sc[1];
-        S.m[2][2] = sc[2];
-        M4 X = mul(mul(T, R), S), Xi;
-        if (!inverse4(X, Xi)) failf("Object %s: singular transform", filename.c_str());
+        M4 X, Xi;
+        if (!objectTransform(tr, rot, sc, X, Xi)) failf("Object %s: singular transform", filename.c_str());
+        rdh_parsed_object rec{(int32_t)out->materialIds.size(), (int32_t)(mesh->vertices.size() / 3), restFirstPrim, materialId, {}, {}, {}};
+        for (int k = 0; k < 3; k++) {
+            rec.translate[k] = tr[k];
+            rec.rotate[k] = rot[k];
+            rec.scale[k] = sc[k];
+        }
+        out->objects.push_back(rec);
         // normalMatrix = transpose(mat3(inverse)): n' = normalize(N * n), N[col][row] = Xi[row][col]
         for (size_t i = 0; i < mesh->vertices.size(); i++) {
             V3 p = mesh->vertices[i], n = mesh->normals[i];
@@ -771,4 +806,25 @@ extern "C" int32_t rdh_scene_parse(const char *sceneFile, rdh_texture_decode_fn 
 
 extern "C" void rdh_scene_parse_free(rdh_parsed_scene *s) {
     if (s) delete static_cast<Parsed *>(s->opaque);
+}
+
+extern "C" int32_t rdh_scene_parse_objects(const rdh_parsed_scene *s, int32_t *numObjects, const rdh_parsed_object **objects,
+                                           int32_t *numRestPrims, const float **restVertices, const float **restNormals) {
+    if (!s || !s->opaque || !numObjects || !objects || !numRestPrims || !restVertices || !restNormals) return RDH_HOST_ERR_ARGS;
+    const Parsed *p = static_cast<const Parsed *>(s->opaque);
+    *numObjects = (int32_t)p->objects.size();
+    *objects = p->objects.data();
+    *numRestPrims = (int32_t)(p->restVertices.size() / 9);
+    *restVertices = p->restVertices.data();
+    *restNormals = p->restNormals.data();
+    return 0;
+}
+
+extern "C" int32_t rdh_object_transform(const float translate[3], const float rotateDeg[3], const float scale[3], float xform32[32]) {
+    if (!translate || !rotateDeg || !scale || !xform32) return RDH_HOST_ERR_ARGS;
+    M4 X, Xi{};
+    const bool ok = objectTransform(translate, rotateDeg, scale, X, Xi);
+    memcpy(xform32, &X.m[0][0], 16 * sizeof(float));
+    memcpy(xform32 + 16, &Xi.m[0][0], 16 * sizeof(float));
+    return ok ? 0 : RDH_HOST_ERR_ARGS;
 }

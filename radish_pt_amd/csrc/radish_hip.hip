@@ -32,6 +32,7 @@
 #include "device/kernels_refit.h"
 #include "device/kernels_lbvh.h"
 #include "device/kernels_lights.h"
+#include "device/kernels_pose.h"
 
 using namespace rd;
 
@@ -171,6 +172,18 @@ struct rdh_ctx {
     float *hLightSums = nullptr;     // pinned copy of a rebuild's {sum, 1 / sum}
     hipEvent_t evLights = nullptr;   // recorded after that copy
     bool lightsPending = false;      // a rebuild's sumLightPowerInv has not been folded into ds yet (settleLights)
+
+    // rdh_scene_set_objects / rdh_scene_pose_objects (kernels_pose.h).  The table, the rest pose and the world arrays are scene
+    // allocations; the staging buffers are the context's.
+    std::vector<rdh_object_range> objects;  // host copy of the table, for the checks (empty: no table)
+    std::vector<unsigned> objectStamp;      // per object: the pose call that last listed it (duplicate check in O(count))
+    unsigned poseEpoch = 0;
+    PoseArgs pose{};                 // objects, rest pose and world arrays; the staged fields are filled in per call
+    bool worldStale = false;         // the world arrays are not what the records hold: the next pose seeds them again (k_pose_seed)
+    GrowBuf hPoseStage[2] = {GrowBuf{bufs, true}, GrowBuf{bufs, true}};  // listed objects: pinned {prefix, ids, xforms} of the last two poses
+    hipEvent_t evPoseStage[2] = {nullptr, nullptr};
+    int poseStageNext = 0;
+    GrowBuf dPoseStage{bufs};        // listed objects: where the kernel reads them
 };
 
 namespace {
@@ -859,6 +872,9 @@ int rdh_scene_free(rdh_ctx *c) {
     c->numLights = 0;
     c->prevTris = nullptr;  // tracking ends with the scene (its buffer was one of sceneAllocs)
     c->movedSinceRender = false;
+    c->objects.clear();  // the object table, rest pose and world arrays were scene allocations too
+    c->pose = PoseArgs{};
+    c->worldStale = false;
     return RDH_OK;
 }
 
@@ -880,6 +896,8 @@ void rdh_destroy(rdh_ctx *c) {
     if (c->hLightSums) hipHostFree(c->hLightSums);
     if (c->evLights) hipEventDestroy(c->evLights);
     for (hipEvent_t e : c->evAliasStage)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->evPoseStage)
         if (e) hipEventDestroy(e);
     if (c->sideStream) hipStreamSynchronize(c->sideStream);
     if (c->litStream && c->litStream != c->sideStream) {
@@ -2509,6 +2527,7 @@ int waitSideStreams(rdh_ctx *c) {
 int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
     const int N = c->ds.numPrims;
     const int geomN = std::max(N, c->numLights);
+    c->worldStale = true;  // rdh_scene_pose_objects clears this again when the arrays were its own
     // rdh_scene_track_motion: the first update since the last G-buffer render keeps what that render saw; a later one must not
     TriRec *keep = nullptr;
     if (c->prevTris && !c->movedSinceRender) {
@@ -2901,6 +2920,203 @@ long long rdh_debug_read_lights(rdh_ctx *c, int which, void *hostOut, long long 
         memcpy(static_cast<char *>(hostOut) + 8, n, 8);
     }
     return bytes;
+}
+
+}  // extern "C"
+
+// ---- objects posed on the device (kernels_pose.h) ---------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(rdh_object_range) == sizeof(PoseRange), "rdh_object_range layout");
+
+// Frees the table, the rest pose and the world arrays (scene allocations) of a scene that stays.
+int dropObjects(rdh_ctx *c) {
+    if (c->objects.empty()) return RDH_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // a pose or the update that followed it may still read them
+    const void *parts[] = {c->pose.objects, c->pose.restVertices, c->pose.restNormals, c->pose.worldVertices, c->pose.worldNormals};
+    for (const void *p : parts) {
+        auto it = std::find(c->sceneAllocs.begin(), c->sceneAllocs.end(), p);
+        if (it == c->sceneAllocs.end()) continue;
+        c->sceneAllocs.erase(it);
+        HIP_TRY(c, hipFree(const_cast<void *>(p)));
+    }
+    c->objects.clear();
+    c->pose = PoseArgs{};
+    c->worldStale = false;
+    return RDH_OK;
+}
+
+template <typename T>
+int sceneAlloc(rdh_ctx *c, T **out, size_t bytes) {
+    void *p = nullptr;
+    HIP_TRY(c, hipMalloc(&p, std::max<size_t>(bytes, 16)));
+    c->sceneAllocs.push_back(p);
+    *out = static_cast<T *>(p);
+    return RDH_OK;
+}
+
+// The world arrays as the records hold them, on the context's stream.
+int seedWorld(rdh_ctx *c) {
+    const int N = c->ds.numPrims;
+    hipLaunchKernelGGL(k_pose_seed, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, c->ds.tris, c->ds.attrs, N,
+                       reinterpret_cast<float *>(c->pose.worldVertices), reinterpret_cast<float *>(c->pose.worldNormals));
+    HIP_TRY(c, hipGetLastError());
+    c->worldStale = false;
+    return RDH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_scene_set_objects(rdh_ctx *c, const rdh_object_range *objects, int32_t numObjects, const float *restVertices,
+                          const float *restNormals, int32_t numRestPrims) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_objects: no scene uploaded");
+    if (numObjects < 0) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_objects: numObjects %d", numObjects);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (numObjects == 0) return dropObjects(c);
+    if (!objects || !restVertices || !restNormals || numRestPrims <= 0)
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_set_objects: null table or rest pose");
+    const int N = c->ds.numPrims;
+    std::vector<std::pair<int, int>> spans;  // {firstPrim, end} of the objects that have triangles
+    for (int i = 0; i < numObjects; i++) {
+        const rdh_object_range &o = objects[i];
+        if (o.firstPrim < 0 || o.numPrims < 0 || o.firstPrim > N || o.numPrims > N - o.firstPrim)
+            return fail(c, RDH_ERR_ARGS, "rdh_scene_set_objects: object %d covers triangles [%d, %d + %d) of %d", i, o.firstPrim,
+                        o.firstPrim, o.numPrims, N);
+        if (o.restFirstPrim < 0 || o.restFirstPrim > numRestPrims || o.numPrims > numRestPrims - o.restFirstPrim)
+            return fail(c, RDH_ERR_ARGS, "rdh_scene_set_objects: object %d reads rest triangles [%d, %d + %d) of %d", i, o.restFirstPrim,
+                        o.restFirstPrim, o.numPrims, numRestPrims);
+        if (o.numPrims > 0) spans.emplace_back(o.firstPrim, o.firstPrim + o.numPrims);
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); i++)
+        if (spans[i].first < spans[i - 1].second)
+            return fail(c, RDH_ERR_ARGS, "rdh_scene_set_objects: two objects share triangle %d", spans[i].first);
+    int rc = dropObjects(c);
+    if (rc) return rc;
+    const size_t restBytes = sizeof(PoseVec) * 3 * (size_t)numRestPrims, worldBytes = sizeof(PoseVec) * 3 * (size_t)N;
+    // built aside and committed only when every step went through: a failure leaves the scene without a table and frees its parts
+    PoseArgs a{};
+    PoseRange *dObjects = nullptr;
+    PoseVec *restV = nullptr, *restN = nullptr;
+    const size_t allocsBefore = c->sceneAllocs.size();
+    auto build = [&]() -> int {
+        if (int e = sceneAlloc(c, &dObjects, sizeof(PoseRange) * (size_t)numObjects)) return e;
+        if (int e = sceneAlloc(c, &restV, restBytes)) return e;
+        if (int e = sceneAlloc(c, &restN, restBytes)) return e;
+        if (int e = sceneAlloc(c, &a.worldVertices, worldBytes)) return e;
+        if (int e = sceneAlloc(c, &a.worldNormals, worldBytes)) return e;
+        HIP_TRY(c, hipMemcpy(dObjects, objects, sizeof(PoseRange) * (size_t)numObjects, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(restV, restVertices, restBytes, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(restN, restNormals, restBytes, hipMemcpyHostToDevice));
+        return RDH_OK;
+    };
+    if ((rc = build())) {
+        while (c->sceneAllocs.size() > allocsBefore) {
+            hipFree(c->sceneAllocs.back());
+            c->sceneAllocs.pop_back();
+        }
+        return rc;
+    }
+    a.objects = dObjects;
+    a.restVertices = restV;
+    a.restNormals = restN;
+    c->pose = a;
+    c->objects.assign(objects, objects + numObjects);
+    c->objectStamp.assign((size_t)numObjects, 0u);
+    c->poseEpoch = 0;
+    return seedWorld(c);
+}
+
+int rdh_scene_pose_objects(rdh_ctx *c, const int32_t *objectIds, const float *xforms32, int32_t count, int tree, uint32_t flags,
+                           float envPower) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene || c->objects.empty())
+        return fail(c, RDH_ERR_STATE, "rdh_scene_pose_objects: the scene has no object table (rdh_scene_set_objects)");
+    if (tree != RDH_POSE_REFIT && tree != RDH_POSE_SAH && tree != RDH_POSE_LBVH)
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: unknown tree %d", tree);
+    if (flags & ~RDH_POSE_REBUILD_LIGHTS) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: unknown flags %u", flags);
+    if (count < 0 || (count > 0 && (!objectIds || !xforms32))) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: bad arguments");
+    if ((flags & RDH_POSE_REBUILD_LIGHTS) && c->ds.envTex >= 0 && !(envPower >= 0.f && envPower <= FLT_MAX))  // as rdh_scene_rebuild_lights
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: envPower %g must be finite and not negative", (double)envPower);
+    if (count == 0) return RDH_OK;
+    if (++c->poseEpoch == 0) {  // the stamps have wrapped
+        std::fill(c->objectStamp.begin(), c->objectStamp.end(), 0u);
+        c->poseEpoch = 1;
+    }
+    const int numObjects = (int)c->objects.size();
+    for (int j = 0; j < count; j++) {
+        const int id = objectIds[j];
+        if (id < 0 || id >= numObjects) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: object id %d of %d", id, numObjects);
+        if (c->objectStamp[(size_t)id] == c->poseEpoch) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: object %d is listed twice", id);
+        c->objectStamp[(size_t)id] = c->poseEpoch;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensureTreeHeader(c);
+    if (rc) return rc;
+    if (!c->evPoseStage[0])
+        for (int k = 0; k < 2; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->evPoseStage[k], hipEventDisableTiming));
+
+    // ids, transforms and the prefix sum of the listed objects' workgroup counts, through pinned memory: no host wait except for
+    // the copy of two poses ago (long done, normally)
+    const int s = c->poseStageNext;
+    const size_t stageBytes = sizeof(int) * (2 * (size_t)count + 1) + sizeof(float) * 32 * (size_t)count;
+    HIP_TRY(c, hipEventSynchronize(c->evPoseStage[s]));
+    if ((rc = grow(c, c->hPoseStage[s], (size_t)count, stageBytes, Busy::Nothing))) return rc;
+    if ((rc = grow(c, c->dPoseStage, (size_t)count, stageBytes, Busy::Stream))) return rc;
+    c->poseStageNext ^= 1;
+    int *hPrefix = c->hPoseStage[s].as<int>(), *hIds = hPrefix + count + 1;
+    float *hXf = reinterpret_cast<float *>(hIds + count);
+    long long groups = 0;
+    for (int j = 0; j < count; j++) {
+        hPrefix[j] = (int)groups;
+        groups += poseGroups(c->objects[(size_t)objectIds[j]].numPrims);  // at most 3 N / 256 + count in all: the ranges are disjoint
+    }
+    hPrefix[count] = (int)groups;
+    memcpy(hIds, objectIds, sizeof(int) * (size_t)count);
+    memcpy(hXf, xforms32, sizeof(float) * 32 * (size_t)count);
+
+    if (c->worldStale && (rc = seedWorld(c))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->dPoseStage.p, c->hPoseStage[s].p, stageBytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evPoseStage[s], c->stream));
+    PoseArgs a = c->pose;
+    a.prefix = c->dPoseStage.as<int>();
+    a.ids = a.prefix + count + 1;
+    a.xforms = reinterpret_cast<const float *>(a.ids + count);
+    a.count = count;
+    if (groups > 0) {
+        hipLaunchKernelGGL(k_pose_objects, dim3((unsigned)groups), dim3(kPoseThreads), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+
+    // the world arrays go where a caller's arrays go
+    const float *wv = reinterpret_cast<const float *>(c->pose.worldVertices), *wn = reinterpret_cast<const float *>(c->pose.worldNormals);
+    if (tree == RDH_POSE_REFIT) rc = rdh_scene_refit_geometry(c, wv, wn, nullptr);
+    else rc = updateGeometry(c, wv, wn, nullptr, tree == RDH_POSE_LBVH ? RDH_BVH_LBVH : RDH_BVH_SAH, "rdh_scene_pose_objects");
+    if (rc) {
+        c->worldStale = true;  // the records did not follow the arrays: seed them again before the next pose
+        return rc;
+    }
+    c->worldStale = false;
+    if (flags & RDH_POSE_REBUILD_LIGHTS) return rdh_scene_rebuild_lights(c, envPower);
+    return RDH_OK;
+}
+
+int rdh_debug_read_world(rdh_ctx *c, float *verticesOut, float *normalsOut) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene || c->objects.empty())
+        return fail(c, RDH_ERR_STATE, "rdh_debug_read_world: the scene has no object table (rdh_scene_set_objects)");
+    if (!verticesOut || !normalsOut) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_world: null output");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->worldStale)
+        if (int rc = seedWorld(c)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = sizeof(PoseVec) * 3 * (size_t)c->ds.numPrims;
+    HIP_TRY(c, hipMemcpy(verticesOut, c->pose.worldVertices, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(normalsOut, c->pose.worldNormals, bytes, hipMemcpyDeviceToHost));
+    return RDH_OK;
 }
 
 }  // extern "C"

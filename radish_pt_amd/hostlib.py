@@ -119,6 +119,30 @@ class _ParsedScene(C.Structure):
     ]
 
 
+class _ParsedObject(C.Structure):  # rdh_parsed_object
+    _fields_ = [("firstPrim", C.c_int32), ("numPrims", C.c_int32), ("restFirstPrim", C.c_int32), ("materialId", C.c_int32),
+                ("translate", C.c_float * 3), ("rotate", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
+# numpy view of rdh_parsed_object[]: parse_scene's "objects"
+OBJECT_DTYPE = np.dtype([("firstPrim", "<i4"), ("numPrims", "<i4"), ("restFirstPrim", "<i4"), ("materialId", "<i4"),
+                         ("translate", "<f4", (3,)), ("rotate", "<f4", (3,)), ("scale", "<f4", (3,))])
+assert OBJECT_DTYPE.itemsize == C.sizeof(_ParsedObject) == 52
+
+
+def object_transform(translate, rotate_deg, scale):
+    """Translate / Rotate (degrees) / Scale of a scene file's Object block -> float32[32]: X = T*R*S, then inverse(X), both
+    column-major, exactly the matrices the loader applies (rdh_object_transform).  Raises ValueError for a singular transform."""
+    l = lib()
+    l.rdh_object_transform.restype = C.c_int32
+    l.rdh_object_transform.argtypes = [C.c_void_p] * 4
+    t, r, s = (np.ascontiguousarray(a, dtype=np.float32).reshape(3) for a in (translate, rotate_deg, scale))
+    out = np.zeros(32, np.float32)
+    if l.rdh_object_transform(t.ctypes.data, r.ctypes.data, s.ctypes.data, out.ctypes.data) != 0:
+        raise ValueError(f"object_transform: translate {t.tolist()} rotate {r.tolist()} scale {s.tolist()} is singular")
+    return out
+
+
 _DECODE_FN = C.CFUNCTYPE(C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.c_int32),
                          C.POINTER(C.c_int32), C.c_void_p)
 
@@ -147,12 +171,17 @@ def _pillow_decode(path, flip_y, rgb_out, w_out, h_out, _user):
 
 def parse_scene(path):
     """rdh_scene_parse → dict of numpy copies: vertices/normals/texcoords/material_ids/materials/textures (list of [h,w,3]),
-    env_map_tex_id, camera (CAMERA_DTYPE scalar or None), trace_depth, iterations, image_name."""
+    env_map_tex_id, camera (CAMERA_DTYPE scalar or None), trace_depth, iterations, image_name; objects (OBJECT_DTYPE[], the
+    Object blocks in file order) with rest_vertices / rest_normals ([3*numRestPrims, 3], the meshes before their transforms:
+    rdh_scene_parse_objects)."""
     l = lib()
     l.rdh_scene_parse.restype = C.c_int32
     l.rdh_scene_parse.argtypes = [C.c_char_p, _DECODE_FN, C.c_void_p, C.POINTER(C.POINTER(_ParsedScene)), C.c_char_p, C.c_int32]
     l.rdh_scene_parse_free.restype = None
     l.rdh_scene_parse_free.argtypes = [C.POINTER(_ParsedScene)]
+    l.rdh_scene_parse_objects.restype = C.c_int32
+    l.rdh_scene_parse_objects.argtypes = [C.POINTER(_ParsedScene), C.POINTER(C.c_int32), C.POINTER(C.POINTER(_ParsedObject)),
+                                          C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float))]
     out = C.POINTER(_ParsedScene)()
     err = C.create_string_buffer(1024)
     cb = _DECODE_FN(_pillow_decode)
@@ -176,6 +205,18 @@ def parse_scene(path):
             "trace_depth": int(s.traceDepth), "iterations": int(s.iterations),
             "image_name": s.imageName.decode(errors="replace"),
         }
+        n_obj, n_rest = C.c_int32(0), C.c_int32(0)
+        objs, rest_v, rest_n = C.POINTER(_ParsedObject)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)()
+        rc = l.rdh_scene_parse_objects(out, C.byref(n_obj), C.byref(objs), C.byref(n_rest), C.byref(rest_v), C.byref(rest_n))
+        if rc != 0:
+            raise RuntimeError(f"rdh_scene_parse_objects({path}) failed: {rc}")
+        res["objects"] = np.frombuffer(C.string_at(objs, OBJECT_DTYPE.itemsize * n_obj.value), dtype=OBJECT_DTYPE).copy()
+        if n_rest.value:
+            res["rest_vertices"] = np.ctypeslib.as_array(rest_v, (3 * n_rest.value, 3)).copy()
+            res["rest_normals"] = np.ctypeslib.as_array(rest_n, (3 * n_rest.value, 3)).copy()
+        else:
+            res["rest_vertices"] = np.zeros((0, 3), np.float32)
+            res["rest_normals"] = np.zeros((0, 3), np.float32)
     finally:
         l.rdh_scene_parse_free(out)
     return res

@@ -84,6 +84,8 @@ class SceneData:
             self.light_sampler = np.zeros(0, dtype=L.BINOMIAL_DTYPE)
             self.sum_light_power_inv = np.float32(0)
         self.sobol = sobol_table()
+        # the object table and rest pose of a scene file (load_scene_file; Context.set_objects); procedural scenes have none
+        self.objects = self.rest_vertices = self.rest_normals = None
 
     def nbytes(self):
         return sum(
@@ -356,9 +358,11 @@ def load_scene_file(path):
     """A Radish scene text file (+ the OBJ meshes and textures it names) → (SceneData, camera, settings dict).
     `Scene::Scene` + `Scene::buildDevData` (/root/reference/src/scene.cpp:108-141,190-249): parsing, mesh/texture loading
     and flattening happen in libradish_host.so (rdh_scene_parse); SceneData then builds the BVH, the light list and the
-    alias tables exactly as for the procedural scenes."""
+    alias tables exactly as for the procedural scenes.  The returned SceneData carries the file's object table and rest pose
+    (`objects`: hostlib.OBJECT_DTYPE[], `rest_vertices`, `rest_normals`) for Context.set_objects / pose_objects."""
     p = hostlib.parse_scene(path)
     sd = SceneData(os.path.basename(path), p["vertices"], p["normals"], p["texcoords"], p["material_ids"], p["materials"],
                    textures=p["textures"], env_map_tex_id=p["env_map_tex_id"])
+    sd.objects, sd.rest_vertices, sd.rest_normals = p["objects"], p["rest_vertices"], p["rest_normals"]
     settings = {"trace_depth": p["trace_depth"], "iterations": p["iterations"], "image_name": p["image_name"]}
     return sd, p["camera"], settings
