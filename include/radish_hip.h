@@ -305,6 +305,22 @@ int rdh_untile(rdh_ctx *ctx, const float *d_gathered, float *d_frame);
  * (the caller / shim owns the globals).  looper = State::looper, maxDepth = Settings::traceDepth. */
 int rdh_path_trace(rdh_ctx *ctx, float *d_directIllum, float *d_indirectIllum, int iter, int looper, int maxDepth,
                    uint32_t flags);
+/* numSamples samples per pixel in one call (the reference's `accumulate` loop, src/main.cpp, in the library).  Afterwards the images
+ * and, with RDH_PT_COUNT, the work counters are bit for bit those of
+ *     for s in 0..numSamples-1: rdh_path_trace(ctx, d, i, iter + s, (looper + s) % 10000, maxDepth, flags)
+ * (the wrap is State::looper's, src/pathtrace.cu:380-381); numSamples == 1 is rdh_path_trace.  Arguments are checked as there;
+ * numSamples < 1 or samplesPerPass < 0: RDH_ERR_ARGS, nothing enqueued.
+ * With RDH_PT_WAVEFRONT, samplesPerPass samples share one pipeline pass: raygen - (trace - shade) x (maxDepth + 1) - finish over
+ * samplesPerPass x the frame's path slots, so that every stage carries that many times the rays and ends on ONE tail instead of
+ * one per sample.  Passes run in order on the context's stream over one workspace; the last takes the remainder.  A value above
+ * numSamples is clamped to it.  One pass holds fewer than 2^30 path slots (64 per 8x8 block of this rank's tiles, per sample) and
+ * at most 4 GiB of them at 164 B each (the workspace keeps its size afterwards; the sub-frame workspaces hold as much again): an
+ * explicit samplesPerPass beyond either is RDH_ERR_ARGS, nothing allocated.  0: the library picks (16, measured; within
+ * both limits).  The other structures (RDH_PT_PERSISTENT, RDH_PT_MEGAKERNEL) run one launch per sample, back to back, and ignore
+ * samplesPerPass.  RDH_PT_AUTO picks the structure as rdh_path_trace does, not by the sample count.  The tile partition is
+ * honoured as in rdh_path_trace (packed tiles).  The last-kernel time covers all passes (wavefront) or the last launch (others). */
+int rdh_path_trace_samples(rdh_ctx *ctx, float *d_directIllum, float *d_indirectIllum, int iter, int looper, int numSamples,
+                           int samplesPerPass, int maxDepth, uint32_t flags);
 /* Replaces pathTraceDirect(glm::vec3*, int) (src/pathtrace.cu:387-407). */
 int rdh_path_trace_direct(rdh_ctx *ctx, float *d_directIllum, int iter, int looper, uint32_t flags);
 /* Replaces GBuffer::render(DevScene*, const Camera&) (src/gBuffer.cu:83-103). */

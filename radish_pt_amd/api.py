@@ -6,6 +6,7 @@ Same names, argument meaning and side effects as the reference's C++ free functi
     Settings.traceDepth, Settings.reservoirReuse, State.looper, State.scene
     pathTraceInit() / pathTraceFree()
     pathTrace(directIllum, indirectIllum, iter)          # advances State.looper mod 10000
+    pathTraceSamples(directIllum, indirectIllum, iter, samples)   # `samples` pathTrace calls' worth in one call
     pathTraceDirect(directIllum, iter)
     ReSTIRInit() / ReSTIRFree() / ReSTIRDirect(directIllum, iter, gBuffer)
     GBuffer.create(w, h) / destroy() / render(devScene, cam) / update(cam)
@@ -56,7 +57,7 @@ SOBOL_SAMPLE_NUM = 10000  # SobolSampleNum, src/sampler.h:12
 # Every symbol include/radish_hip.h declares (tests check that the library exports all of them).
 EXPORTS = [
     "rdh_create", "rdh_destroy", "rdh_last_error", "rdh_set_stream", "rdh_synchronize", "rdh_scene_upload",
-    "rdh_scene_free", "rdh_set_camera", "rdh_set_partition", "rdh_tiles_per_rank", "rdh_untile", "rdh_path_trace",
+    "rdh_scene_free", "rdh_set_camera", "rdh_set_partition", "rdh_tiles_per_rank", "rdh_untile", "rdh_path_trace", "rdh_path_trace_samples",
     "rdh_path_trace_direct", "rdh_gbuffer_render", "rdh_restir_init", "rdh_restir_free", "rdh_restir_direct",
     "rdh_restir_read", "rdh_restir_read_scratch", "rdh_copy_image_to_pbo", "rdh_denoise_eaw", "rdh_denoise_svgf", "rdh_denoise_modulate",
     "rdh_denoise_add", "rdh_denoise_temporal_accumulate", "rdh_denoise_estimate_variance", "rdh_denoise_filter_variance", "rdh_restir_exchange_pack", "rdh_restir_exchange_unpack", "rdh_trace_closest", "rdh_trace_occluded", "rdh_counters_reset", "rdh_counters_read",
@@ -144,6 +145,7 @@ def lib():
             "rdh_tiles_per_rank": ([vp], i32),
             "rdh_untile": ([vp, vp, vp], i32),
             "rdh_path_trace": ([vp, vp, vp, i32, i32, i32, u32], i32),
+            "rdh_path_trace_samples": ([vp, vp, vp, i32, i32, i32, i32, i32, u32], i32),
             "rdh_path_trace_direct": ([vp, vp, i32, i32, u32], i32),
             "rdh_gbuffer_render": ([vp, C.POINTER(GBufferC), u32], i32),
             "rdh_restir_init": ([vp], i32),
@@ -522,6 +524,14 @@ class Context:
         self.check(lib().rdh_path_trace(self.h, self._ptr(direct, n, "pathTrace: directIllum"),
                                         self._ptr(indirect, n, "pathTrace: indirectIllum"), iter, looper, max_depth, flags))
 
+    def path_trace_samples(self, direct, indirect, iter, looper, samples, max_depth, flags=RDH_PT_PERSISTENT, samples_per_pass=0):
+        """`samples` samples per pixel (rdh_path_trace_samples): the images afterwards are those of path_trace at iter + s, looper
+        (looper + s) % 10000 for s = 0..samples-1.  Wavefront: samples_per_pass samples share one pipeline pass (0: the library picks)."""
+        n = self._image_elems()
+        self.check(lib().rdh_path_trace_samples(self.h, self._ptr(direct, n, "pathTraceSamples: directIllum"),
+                                                self._ptr(indirect, n, "pathTraceSamples: indirectIllum"), iter, looper, samples,
+                                                samples_per_pass, max_depth, flags))
+
     def path_trace_direct(self, direct, iter, looper, flags=0):
         n = self._image_elems() if self.width else 0
         self.check(lib().rdh_path_trace_direct(self.h, self._ptr(direct, n, "pathTraceDirect: directIllum"), iter, looper, flags))
@@ -864,6 +874,15 @@ def pathTrace(directIllum, indirectIllum, iter):
     ctx.path_trace(directIllum, indirectIllum, iter, State.looper, Settings.traceDepth, Settings.ptFlags)
     ctx.synchronize()
     _advance_looper()
+
+
+def pathTraceSamples(directIllum, indirectIllum, iter, samples):
+    """`samples` samples per pixel in one call: the images and State.looper afterwards are those of pathTrace at iter,
+    iter + 1, ..., iter + samples - 1 (the reference's `accumulate` loop).  Blocking."""
+    ctx = _ctx()
+    ctx.path_trace_samples(directIllum, indirectIllum, iter, State.looper, samples, Settings.traceDepth, Settings.ptFlags)
+    ctx.synchronize()
+    State.looper = (State.looper + samples) % SOBOL_SAMPLE_NUM
 
 
 def pathTraceDirect(directIllum, iter):

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -40,6 +41,14 @@ constexpr int kWfParts = 3;  // sub-frame pipelines of the wavefront path at mos
 constexpr int kWfPartsDefault = 1;  // ... by default: see wavefrontPathTrace
 // Sub-frame pipelines together hold at most this many bytes of pair-walker overflow strips; beyond it the frame is one pipeline.
 constexpr size_t kWfStripBudget = size_t(512) << 20;
+// rdh_path_trace_samples: what one pass of the wavefront pipeline may hold.  Fewer than 2^30 path slots (the queues encode
+// -2 - slot, and bit 30 marks a shadow ray on the first lists), and at most kWfSampleBudget bytes of them at kWfSlotBytes each
+// (152 B of path state + three queue entries; the sub-frame workspaces, two halves, add as much again).  kWfSamplesPerPass is the
+// library's choice within both (samplesPerPass = 0; measured: DESIGN 5f).
+constexpr long long kWfMaxSlots = 1ll << 30;
+constexpr size_t kWfSlotBytes = 164;
+constexpr size_t kWfSampleBudget = size_t(4) << 30;
+constexpr int kWfSamplesPerPass = 16;
 
 // A device (or pinned host) buffer that grows on demand (grow(), below) and dies with its context: each one enters itself in
 // rdh_ctx::bufs, which rdh_destroy walks.
@@ -596,14 +605,16 @@ int wfAlloc(rdh_ctx *c, T **out, size_t count) {
 }
 
 // Workspace for the wavefront pipeline: 152 B of path state + the ray / shadow queue entries per path slot, per sub-frame, plus
-// the two literal-class lists (litq) of kWfLitCap entries.
-int wavefrontEnsure(rdh_ctx *c, const PixelMap &pm) {
-    long long slots = (long long)pm.numBlocks * 64;  // workspace 0: the whole frame; 1 and 2: a third each (+ a block), sized for half
+// the two literal-class lists (litq) of kWfLitCap entries.  `samples`: how many samples of every pixel a launch carries.
+int wavefrontEnsure(rdh_ctx *c, const PixelMap &pm, int samples) {
+    long long slots = (long long)pm.numBlocks * 64 * samples;  // workspace 0: the whole frame; 1 and 2: a third each (+ a block), sized for half
     if (c->wfCapacity >= slots) return RDH_OK;
     for (void *p : c->wfAllocs) hipFree(p);
     c->wfAllocs.clear();
     c->wfCapacity = 0;
-    const size_t n0 = (size_t)slots, n1 = (size_t)((pm.numBlocks + 1) / 2) * 64;
+    // (half of the slots, not of the blocks: a later frame of fewer blocks and more samples may fit the capacity, and its sub-frames
+    // 1 and 2 hold at most numBlocks / 2 blocks' worth of it)
+    const size_t n0 = (size_t)slots, n1 = (size_t)((slots / 64 + 1) / 2) * 64;
     for (int h = 0; h < kWfParts; h++) {
         WaveWorkspace &w = c->wf[h];
         const size_t n = h == 0 ? n0 : n1;  // workspace 0 also serves the one-pipeline mode (whole frame)
@@ -627,7 +638,9 @@ int wavefrontEnsure(rdh_ctx *c, const PixelMap &pm) {
     return RDH_OK;
 }
 
-int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d_indirect, int iter, int looper,
+// One pipeline pass over `samples` samples of every pixel: Sobol rows looper, looper + 1, ... (mod 10000), folded into the running
+// means as iter, iter + 1, ... (k_wf_raygen, k_wf_finish).
+int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d_indirect, int iter, int looper, int samples,
                        int maxDepth, uint32_t flags) {
     if (maxDepth > kMaxWaveDepth) return fail(c, RDH_ERR_ARGS, "maxDepth %d exceeds %d", maxDepth, kMaxWaveDepth);
     const bool count = (flags & RDH_PT_COUNT) != 0, sort = (flags & RDH_PT_SORT_MATERIAL) != 0;
@@ -688,9 +701,9 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
         hipStream_t st = sts[h];
         WaveWorkspace &w = c->wf[h];
         const unsigned nLocal = (unsigned)(pm.numBlocks - h + parts - 1) / (unsigned)parts;
-        const unsigned gridBlk = (((nLocal + 3u) / 4u + 7u) / 8u) * 8u;
+        const unsigned gridBlk = (((nLocal * (unsigned)samples + 3u) / 4u + 7u) / 8u) * 8u;
         keep(hipMemsetAsync(w.ctr, 0, sizeof(WaveCounters), st), "hipMemsetAsync(wavefront counters)");
-        hipLaunchKernelGGL(k_wf_raygen, dim3(gridBlk), dim3(256), 0, st, c->ds, c->cam, pm, w, looper, h, parts);
+        hipLaunchKernelGGL(k_wf_raygen, dim3(gridBlk), dim3(256), 0, st, c->ds, c->cam, pm, w, looper, samples, h, parts);
     }
     for (int k = 0; k <= maxDepth && rc == RDH_OK; k++) {
         for (int h = 0; h < parts; h++) {  // interleaved issue: stage k of every pipeline before stage k + 1 of any
@@ -709,7 +722,7 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
         hipStream_t st = sts[h];
         const unsigned nLocal = (unsigned)(pm.numBlocks - h + parts - 1) / (unsigned)parts;
         const unsigned gridBlk = (((nLocal + 3u) / 4u + 7u) / 8u) * 8u;
-        hipLaunchKernelGGL(k_wf_finish, dim3(gridBlk), dim3(256), 0, st, pm, c->wf[h], iter, d_direct, d_indirect, h, parts);
+        hipLaunchKernelGGL(k_wf_finish, dim3(gridBlk), dim3(256), 0, st, pm, c->wf[h], iter, samples, d_direct, d_indirect, h, parts);
     }
     keep(hipGetLastError(), "k_wf_finish");
     if (parts >= 2) {  // the join is unconditional; if it cannot be expressed with events the side streams are drained
@@ -732,6 +745,14 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
 int ensureStackOverflow(rdh_ctx *c, unsigned resident) {
     const size_t ints = (size_t)resident * 64 * (size_t)(c->ds.treeDepth + 1) * 2;  // int2 entries, by entry number (pairPush)
     return grow(c, c->treeOvf, ints, ints * sizeof(int), Busy::Device);
+}
+
+// RDH_PT_AUTO: the structure by what a launch holds (radish_hip.h; measured: DESIGN 5d, 8)
+uint32_t resolveStructure(const rdh_ctx *c, const PixelMap &pm, uint32_t flags) {
+    if (!(flags & RDH_PT_AUTO)) return flags;
+    flags &= ~(RDH_PT_AUTO | RDH_PT_WAVEFRONT | RDH_PT_SORT_MATERIAL | RDH_PT_WF_SUBFRAMES | RDH_PT_PERSISTENT);
+    const bool wavefront = c->ds.bvhSize >= 100000 && pm.numBlocks >= 12000;
+    return flags | (wavefront ? (RDH_PT_WAVEFRONT | RDH_PT_SORT_MATERIAL | RDH_PT_WF_SUBFRAMES) : RDH_PT_PERSISTENT);
 }
 
 int packetBudget(uint32_t flags) { return (flags & RDH_PT_WF_SMALL_LISTS) ? 4 : kPacketBudget; }  // tests: packets of 4 visits
@@ -1188,16 +1209,12 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
     HIP_TRY(c, hipSetDevice(c->device));
     PixelMap pm = makePixelMap(c);
     const bool count = (flags & RDH_PT_COUNT) != 0;
-    if (flags & RDH_PT_AUTO) {  // the structure by what this launch holds (radish_hip.h; measured: DESIGN 5d, 8)
-        flags &= ~(RDH_PT_AUTO | RDH_PT_WAVEFRONT | RDH_PT_SORT_MATERIAL | RDH_PT_WF_SUBFRAMES | RDH_PT_PERSISTENT);
-        const bool wavefront = c->ds.bvhSize >= 100000 && pm.numBlocks >= 12000;
-        flags |= wavefront ? (RDH_PT_WAVEFRONT | RDH_PT_SORT_MATERIAL | RDH_PT_WF_SUBFRAMES) : RDH_PT_PERSISTENT;
-    }
+    flags = resolveStructure(c, pm, flags);
     if (flags & RDH_PT_WAVEFRONT) {
-        rc = wavefrontEnsure(c, pm);
+        rc = wavefrontEnsure(c, pm, 1);
         if (rc) return rc;
         timeBegin(c);
-        rc = wavefrontPathTrace(c, pm, d_direct, d_indirect, iter, looper, maxDepth, flags);
+        rc = wavefrontPathTrace(c, pm, d_direct, d_indirect, iter, looper, 1, maxDepth, flags);
         if (rc) return rc;
         return timeEnd(c, "pathTrace (wavefront)");
     }
@@ -1273,6 +1290,43 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
     }, count);
     profEnd(c, pe);
     return timeEnd(c, "pathTrace");
+}
+
+int rdh_path_trace_samples(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int looper, int numSamples, int samplesPerPass,
+                           int maxDepth, uint32_t flags) {
+    int rc = requireReady(c);
+    if (rc) return rc;
+    if (!d_direct || !d_indirect || iter < 0 || looper < 0 || looper >= kSobolRows || maxDepth < 0 || numSamples < 1 ||
+        samplesPerPass < 0 || iter > INT_MAX - numSamples)
+        return fail(c, RDH_ERR_ARGS, "rdh_path_trace_samples: bad arguments");
+    if (4 + 7 * maxDepth > 200) return fail(c, RDH_ERR_ARGS, "maxDepth %d needs more than 200 Sobol dimensions", maxDepth);
+    const PixelMap pm = makePixelMap(c);
+    flags = resolveStructure(c, pm, flags);
+    if (!(flags & RDH_PT_WAVEFRONT)) {  // one launch per sample, back to back: the other structures hold one sample of a pixel at a time
+        for (int s = 0; s < numSamples; s++)
+            if ((rc = rdh_path_trace(c, d_direct, d_indirect, iter + s, (looper + s) % kSobolRows, maxDepth, flags))) return rc;
+        return RDH_OK;
+    }
+    if (maxDepth > kMaxWaveDepth) return fail(c, RDH_ERR_ARGS, "maxDepth %d exceeds %d", maxDepth, kMaxWaveDepth);
+    // samples per pass: the caller's (checked against both caps) or the library's (held within them)
+    const long long frameSlots = (long long)pm.numBlocks * 64;
+    // (one sample per pass is rdh_path_trace and always allowed, whatever the frame)
+    const long long cap = std::max(1ll, std::min((kWfMaxSlots - 1) / frameSlots, (long long)(kWfSampleBudget / kWfSlotBytes) / frameSlots));
+    int perPass = std::min(samplesPerPass ? samplesPerPass : kWfSamplesPerPass, numSamples);
+    if (perPass > cap) {
+        if (samplesPerPass)
+            return fail(c, RDH_ERR_ARGS, "rdh_path_trace_samples: %d samples per pass of %lld path slots each: a pass holds fewer than 2^30 "
+                        "slots and at most %zu MiB of them (%lld samples here)", perPass, frameSlots, kWfSampleBudget >> 20, cap);
+        perPass = (int)cap;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = wavefrontEnsure(c, pm, perPass))) return rc;
+    timeBegin(c);
+    for (int s = 0; s < numSamples; s += perPass) {  // in order on the context's stream, over one workspace
+        const int b = std::min(perPass, numSamples - s);
+        if ((rc = wavefrontPathTrace(c, pm, d_direct, d_indirect, iter + s, (looper + s) % kSobolRows, b, maxDepth, flags))) return rc;
+    }
+    return timeEnd(c, "pathTrace (wavefront)");
 }
 
 int rdh_path_trace_direct(rdh_ctx *c, float *d_direct, int iter, int looper, uint32_t flags) {

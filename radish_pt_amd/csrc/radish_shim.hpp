@@ -195,6 +195,25 @@ inline void pathTrace(glm::vec3 *directIllum, glm::vec3 *indirectIllum, int iter
     State::looper = (State::looper + 1) % 10000;                                          // :380-381
 }
 
+// `samples` samples per pixel in one call (no reference counterpart; its `accumulate` loop calls pathTrace once per sample): the images
+// afterwards are those of pathTrace at iter, iter + 1, ..., and State::looper has advanced `samples` times.  On one GPU the library
+// batches the samples (rdh_path_trace_samples); the gathered multi-GPU entries take one sample per call.
+inline void pathTraceSamples(glm::vec3 *directIllum, glm::vec3 *indirectIllum, int iter, int samples) {
+#if defined(RADISH_SHIM_ONE_PROCESS_GPUS) || defined(RADISH_SHIM_MULTI_GPU)
+    for (int s = 0; s < samples; s++) pathTrace(directIllum, indirectIllum, iter + s);
+#else
+    rdh_ctx *c = radish_shim::ctx();
+    RADISH_CHECK(rdh_set_camera(c, &State::scene->camera), "pathTraceSamples");
+    RADISH_CHECK(rdh_path_trace_samples(c, reinterpret_cast<float *>(directIllum), reinterpret_cast<float *>(indirectIllum), iter,
+                                        State::looper, samples, 0, Settings::traceDepth, RDH_PT_AUTO),
+                 "pathTraceSamples");
+    RADISH_CHECK(rdh_synchronize(c), "pathTraceSamples");
+    float ms = 0.f;
+    if (rdh_last_kernel_ms(c, &ms) == RDH_OK) std::printf("PT runtime%.3f ms\n", ms);
+    State::looper = (State::looper + samples) % 10000;
+#endif
+}
+
 inline void pathTraceDirect(glm::vec3 *directIllum, int iter) {
     rdh_ctx *c = radish_shim::ctx();
     RADISH_CHECK(rdh_set_camera(c, &State::scene->camera), "pathTraceDirect");
