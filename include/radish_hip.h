@@ -172,7 +172,7 @@ int rdh_scene_upload(rdh_ctx *ctx, const rdh_scene_desc *desc);
  * rdh_scene_upload (not checked here: that would need the vertices on the host). */
 typedef struct rdh_light_update {
     const void *lightSampler;   /* HOST BinomialDistrib<float>[lightSamplerLength], as in rdh_scene_desc              */
-    int32_t lightSamplerLength; /* must equal the uploaded scene's                                                   */
+    int32_t lightSamplerLength; /* must equal the scene's current (rdh_scene_set_materials changes it)               */
     float sumLightPowerInv;
 } rdh_light_update;
 int rdh_build_bvh_device(rdh_ctx *ctx, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]);
@@ -238,14 +238,16 @@ long long rdh_debug_read_tree(rdh_ctx *ctx, int which, void *hostOut, long long 
  * Asynchronous on the context's stream: sumLightPowerInv reaches the host the way an update's tree header does, and the next render
  * call waits for it before it launches.  Call it after an update or refit that was given lights = NULL, or at any other time; a
  * later update that brings a rdh_light_update replaces what a rebuild still in flight computes.  Scratch is allocated by the first
- * rebuild of a scene, sized by lightSamplerLength.  ReSTIR reservoirs are kept.  No scene, or (on a scene with an environment map)
+ * rebuild of a scene, sized by the lightSamplerLength the scene's arrays hold.  ReSTIR reservoirs are kept.  No scene, or (on a scene with an environment map)
  * an envPower that is negative or not finite: RDH_ERR_ARGS, the scene unchanged and nothing enqueued.  Without an environment map
  * envPower is ignored; lightSamplerLength == 0: RDH_OK, nothing done.
  * rdh_debug_read_lights: test access to the light sampler the kernels read: which = 0 the alias table (lightSamplerLength x 8 B),
  * 1 {float sum, sumLightPowerInv; int32 lightSamplerLength, numLights} (16 B; sum is 1.f / sumLightPowerInv, the reciprocal of the
  * frame kernels' argument as it stands: an upload brings only that value), 2 the per-light constants (numLights x 64 B: the
- * emissive triangle's record, its normal and power * sumLightPowerInv).  Returns the byte size (hostOut NULL: only that) or a
- * negative RDH_ERR_*.  Blocking; folds a rebuild still in flight in first, like rdh_debug_read_tree. */
+ * emissive triangle's record, its normal and power * sumLightPowerInv), 4 the current lightPrimIds (numLights x 4 B; 3 is not a selector and stays RDH_ERR_ARGS).  Returns the
+ * byte size (hostOut NULL: only that) or a negative RDH_ERR_*.  Blocking; folds a rebuild still in flight in first, like
+ * rdh_debug_read_tree.  After an rdh_scene_set_materials that derived the list again it also compares the device's own emitter
+ * count with the host's (RDH_ERR_STATE when they differ). */
 int rdh_build_alias_table_device(rdh_ctx *ctx, const float *d_values, int32_t n, void *d_table, float *d_sum);
 int rdh_scene_rebuild_lights(rdh_ctx *ctx, float envPower);
 long long rdh_debug_read_lights(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
@@ -285,6 +287,37 @@ int rdh_scene_set_objects(rdh_ctx *ctx, const rdh_object_range *objects, int32_t
 int rdh_scene_pose_objects(rdh_ctx *ctx, const int32_t *objectIds, const float *xforms32, int32_t count, int tree, uint32_t flags,
                            float envPower);
 int rdh_debug_read_world(rdh_ctx *ctx, float *verticesOut, float *normalsOut);
+/* ---- materials edited on the device ------------------------------------------------------------------------------------
+ * A scene whose materials were edited here is, bit for bit, the scene a fresh rdh_scene_upload of the edited description gives
+ * (the alias table's NaN payloads aside, as for rdh_build_alias_table_device).
+ * rdh_scene_set_materials: materialIds int32[count] (HOST, each at most once), materials Material[count] (HOST, 44 B each, as in
+ * rdh_scene_desc): the listed materials of the uploaded scene are replaced.  Triangles keep their material ids.  On the context's
+ * stream: the listed material records and every triangle's shading class (the wavefront material sort's key) are rewritten; when
+ * the set of Light materials changes, or a Light's colour does, the emissive-triangle list is derived again on the device (in
+ * ascending triangle order, radiance = the material's colour: what rdh_build_light_list and the upload's packing write), and
+ * what rdh_scene_rebuild_lights(ctx, envPower) does follows: powers, alias table, per-light constants, sumLightPowerInv.  The
+ * light count is known on the host at once (the context keeps the materials and how many triangles carry each), so
+ * lightSamplerLength = numLights (+ 1 with an environment map) changes with the call, and a rdh_light_update, an update, a refit,
+ * a pose, a rebuild or a debug read that follows sees the current list and length.  A list longer than the scene's arrays hold
+ * reallocates them, which waits for the stream; a shorter one frees nothing.  An edit that leaves no light on a scene without an
+ * environment map sets lightSamplerLength = 0 and sumLightPowerInv = 0.  No host wait in the steady state: ids and materials go
+ * through pinned memory (O(count)), and the call waits only for the staging copy of two edits ago.  The tree, the pairs, the refit
+ * plan, the object table and world arrays, motion tracking and the persistent block order are kept, and so are ReSTIR reservoirs:
+ * a caller who switches emitters should call rdh_restir_init, as after every other scene edit that changes the lights.  Checked
+ * before anything is enqueued, the scene unchanged: no scene RDH_ERR_NO_SCENE; an id out of range or listed twice, null pointers
+ * with count > 0, a map id rdh_scene_upload would refuse (it must name one of the uploaded textures, -1, or -2 for a base
+ * colour), an envPower rdh_scene_rebuild_lights would refuse: RDH_ERR_ARGS.  count == 0: RDH_OK, nothing enqueued.
+ * Out of scope: giving triangles other material ids, and editing textures; both still take rdh_scene_upload.
+ * rdh_build_light_list_device: the device twin of rdh_build_light_list (include/radish_host.h) — d_vertices float[3*numPrims][3],
+ * d_materialIds int32[numPrims], d_materials Material[numMaterials] -> d_lightPrimIds int32[], d_lightUnitRadiance float[][3],
+ * d_lightPower float[] (each with room for numPrims entries; the first *d_count are written) and *d_count, bit for bit what the
+ * host function writes.  A material id out of range makes *d_count -1 (the host function's RDH_HOST_ERR_ARGS) and leaves the
+ * arrays unspecified; numPrims == 0: *d_count = 0.  Device pointers; asynchronous on the context's stream; needs no scene; its
+ * scratch grows with numPrims (growing it waits for the stream).  Negative sizes or a null pointer: RDH_ERR_ARGS. */
+int rdh_scene_set_materials(rdh_ctx *ctx, const int32_t *materialIds, const void *materials, int32_t count, float envPower);
+int rdh_build_light_list_device(rdh_ctx *ctx, const float *d_vertices, const int32_t *d_materialIds, int32_t numPrims,
+                                const void *d_materials, int32_t numMaterials, int32_t *d_lightPrimIds, float *d_lightUnitRadiance,
+                                float *d_lightPower, int32_t *d_count);
 /* Replaces DevScene::destroy (src/scene.cpp:553-574). */
 int rdh_scene_free(rdh_ctx *ctx);
 /* The `Camera cam` kernel argument of every reference kernel (State::scene->camera, src/pathtrace.cu:356). */

@@ -72,6 +72,7 @@ EXPORTS = [
     "rdh_scene_track_motion",
     "rdh_build_alias_table_device", "rdh_scene_rebuild_lights", "rdh_debug_read_lights",
     "rdh_scene_set_objects", "rdh_scene_pose_objects", "rdh_debug_read_world",
+    "rdh_scene_set_materials", "rdh_build_light_list_device",
 ]
 
 
@@ -204,6 +205,8 @@ def lib():
             "rdh_scene_set_objects": ([vp, vp, i32, vp, vp, i32], i32),
             "rdh_scene_pose_objects": ([vp, vp, vp, i32, i32, u32, C.c_float], i32),
             "rdh_debug_read_world": ([vp, vp, vp], i32),
+            "rdh_scene_set_materials": ([vp, vp, vp, i32, C.c_float], i32),
+            "rdh_build_light_list_device": ([vp, vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -420,7 +423,8 @@ class Context:
 
     def debug_read_lights(self, which):
         """Blocking test access (rdh_debug_read_lights): 0 -> the alias table (layouts.BINOMIAL_DTYPE), 1 -> {float32 sum,
-        sumLightPowerInv; int32 lightSamplerLength, numLights} as 16 bytes, 2 -> the LightPre records' bytes."""
+        sumLightPowerInv; int32 lightSamplerLength, numLights} as 16 bytes, 2 -> the LightPre records' bytes, 4 -> the current
+        lightPrimIds (int32)."""
         n = lib().rdh_debug_read_lights(self.h, which, None, 0)
         if n < 0:
             self.check(int(n))
@@ -429,7 +433,53 @@ class Context:
             rc = lib().rdh_debug_read_lights(self.h, which, out.ctypes.data, n)
             if rc < 0:
                 self.check(int(rc))
+        if which == 4:
+            return out.view(np.int32)
         return out.view(L.BINOMIAL_DTYPE) if which == 0 else out
+
+    # ---- materials edited on the device ----
+    def set_materials(self, ids, materials, env_power=0.0):
+        """Replace the listed materials of the uploaded scene (rdh_scene_set_materials): ids int32 (each at most once), materials an
+        array of layouts.MATERIAL_DTYPE, one per id.  Triangles keep their material ids.  When the edit changes which materials
+        are lights, or a light's colour, the emissive-triangle list, the alias table, sumLightPowerInv and the per-light constants
+        are derived again on the device (env_power as for rebuild_lights).  The scene then renders like a fresh upload_scene of the
+        edited description.  Does not block in the steady state."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        mats = np.asarray(materials)
+        if mats.dtype != L.MATERIAL_DTYPE:
+            raise RadishError(f"set_materials: materials must be an array of layouts.MATERIAL_DTYPE, got dtype {mats.dtype}")
+        mats = np.ascontiguousarray(mats).reshape(-1)
+        if len(mats) != len(ids):
+            raise RadishError(f"set_materials: {len(ids)} ids but {len(mats)} materials")
+        self.check(lib().rdh_scene_set_materials(self.h, ids.ctypes.data if len(ids) else None, mats.ctypes.data if len(ids) else None,
+                                                 len(ids), float(env_power)))
+
+    def build_light_list_device(self, vertices, material_ids, materials):
+        """vertices float32 cuda tensor of 9*N floats, material_ids int32 cuda tensor [N], materials uint8 cuda tensor holding M
+        layouts.MATERIAL_DTYPE records (44 B each) -> (light_prim_ids int32 [N], light_unit_radiance float32 [N, 3], light_power
+        float32 [N], count int32 [1]) on the device: the first `count` rows are hostlib.build_light_list's, bit for bit; count is
+        -1 when a material id is out of range (rdh_build_light_list_device).  Asynchronous on the context's stream."""
+        torch = _torch()
+        for t, name in ((vertices, "vertices"), (material_ids, "material_ids"), (materials, "materials")):
+            if not isinstance(t, torch.Tensor):
+                raise RadishError(f"build_light_list_device: {name} must be a torch tensor, got {type(t).__name__}")
+        n = material_ids.numel()
+        if vertices.numel() != 9 * n:
+            raise RadishError(f"build_light_list_device: {n} material ids but {vertices.numel()} vertex floats (9 per triangle)")
+        if materials.numel() % L.MATERIAL_DTYPE.itemsize:
+            raise RadishError(f"build_light_list_device: materials must hold whole {L.MATERIAL_DTYPE.itemsize}-byte records")
+        m = materials.numel() // L.MATERIAL_DTYPE.itemsize
+        vp = self._ptr(vertices, 9 * n, "build_light_list_device vertices") if n else None
+        ip = self._ptr(material_ids, n, "build_light_list_device material_ids", torch.int32) if n else None
+        mp = self._ptr(materials, materials.numel(), "build_light_list_device materials", torch.uint8) if n else None
+        dev = f"cuda:{self.device}"
+        prims = torch.empty(n, dtype=torch.int32, device=dev)
+        radiance = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        power = torch.empty(n, dtype=torch.float32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.check(lib().rdh_build_light_list_device(self.h, vp, ip, n, mp, m, prims.data_ptr() if n else None,
+                                                     radiance.data_ptr() if n else None, power.data_ptr() if n else None, count.data_ptr()))
+        return prims, radiance, power, count
 
     # ---- moving geometry: objects posed on the device (DESIGN 11f) ----
     def set_objects(self, sd=None, objects=None, rest_vertices=None, rest_normals=None):

@@ -32,6 +32,15 @@ RD_DEV int laneBelow(unsigned long long mask) {  // set bits of `mask` below thi
 RD_DEV float uniformF(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
 RD_DEV float laneF(float x, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane)); }
 
+// rdh_build_light_list's power of one emissive triangle (scene_build.cpp), operation for operation.
+RD_DEV float emitterPower(v3 v0, v3 v1, v3 v2_, float r, float g, float b) {
+    const float lum = 0.2126f * r + 0.7152f * g + 0.0722f * b;
+    const float powerUnitArea = lum * 2.f * 3.14159265358979323846264338327950288f;
+    const v3 c = cross(v1 - v0, v2_ - v0);
+    const float area = __builtin_sqrtf(dot(c, c)) * 0.5f;
+    return powerUnitArea * area;
+}
+
 // power[i] = luminance(radiance) * 2 * pi * area of light i (scene_build.cpp, rdh_build_light_list); entries numLights .. n - 1 (the
 // environment map's, at most one) = envPower.
 __global__ __launch_bounds__(256) void k_light_power(const LightRec *__restrict__ lights, int numLights, int n, float envPower,
@@ -43,12 +52,7 @@ __global__ __launch_bounds__(256) void k_light_power(const LightRec *__restrict_
         return;
     }
     const float4 A = lights[i].a, B = lights[i].b, C = lights[i].c;
-    const v3 v0 = mk3(A.x, A.y, A.z), v1 = mk3(A.w, B.x, B.y), v2_ = mk3(B.z, B.w, C.x);
-    const float lum = 0.2126f * C.y + 0.7152f * C.z + 0.0722f * C.w;
-    const float powerUnitArea = lum * 2.f * 3.14159265358979323846264338327950288f;
-    const v3 c = cross(v1 - v0, v2_ - v0);
-    const float area = __builtin_sqrtf(dot(c, c)) * 0.5f;
-    power[i] = powerUnitArea * area;
+    power[i] = emitterPower(mk3(A.x, A.y, A.z), mk3(A.w, B.x, B.y), mk3(B.z, B.w, C.x), C.y, C.z, C.w);
 }
 
 // One wave.  The sum's order is fixed (index order), so a tile of 64 values is loaded in one coalesced load and added lane by lane

@@ -104,7 +104,9 @@ __global__ __launch_bounds__(256) void k_refit_count(const NodeRec *__restrict__
     if (threadIdx.x == 0) blockSums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-__global__ __launch_bounds__(256) void k_refit_scan(int *blockSums, int nBlocks) {
+// The exclusive prefix of n block totals, in place, by one 256-lane workgroup that walks them a tile at a time (any n); every lane
+// returns the grand total.  Shared with the emitter compaction (kernels_materials.h).
+RD_DEV int scanBlockTotals(int *blockSums, int nBlocks) {
     __shared__ int s[256];
     __shared__ int carry;
     if (threadIdx.x == 0) carry = 0;
@@ -125,7 +127,10 @@ __global__ __launch_bounds__(256) void k_refit_scan(int *blockSums, int nBlocks)
         if (threadIdx.x == 255) carry += s[255];
         __syncthreads();
     }
+    return carry;
 }
+
+__global__ __launch_bounds__(256) void k_refit_scan(int *blockSums, int nBlocks) { scanBlockTotals(blockSums, nBlocks); }
 
 __global__ __launch_bounds__(256) void k_refit_number(const NodeRec *__restrict__ nodes0, int S, const int *__restrict__ blockOff,
                                                       RefitPlanRec *plan) {

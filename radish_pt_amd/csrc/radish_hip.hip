@@ -34,6 +34,7 @@
 #include "device/kernels_lbvh.h"
 #include "device/kernels_lights.h"
 #include "device/kernels_pose.h"
+#include "device/kernels_materials.h"
 
 using namespace rd;
 
@@ -67,6 +68,14 @@ struct GrowBuf {
         cap = 0;
     }
 };
+
+struct HostMaterial {  // Material (src/material.h:276-286), as rdh_scene_desc::materials holds it
+    int32_t type;
+    float color[3];
+    float metallic, roughness, ior;
+    int32_t map[4];
+};
+static_assert(sizeof(HostMaterial) == 44, "Material layout");
 
 struct rdh_ctx {
     int device = 0;
@@ -154,7 +163,7 @@ struct rdh_ctx {
     GrowBuf bvhScratch{bufs};        // primitives: the BvhWork buffers, one allocation
     GrowBuf lbvhScratch{bufs};       // primitives: the LbvhWork buffers and the BvhWork slot arrays (RDH_BVH_LBVH)
     GrowBuf updTree{bufs};           // primitives: the update's boxes + six int[S][3] orderings
-    int *dLightPrims = nullptr;      // the uploaded scene's lightPrimIds (scene allocation)
+    int *dLightPrims = nullptr;      // the scene's current lightPrimIds (scene allocation; rdh_scene_set_materials rewrites it)
     int numLights = 0;
     PairRec *updPairs = nullptr;     // pairs of an updated tree when the upload had none (scene allocation)
     int4 *dTreeHdr = nullptr;        // k_bvh_pairs' header: {treeDepth, error}, rootLo, rootHi
@@ -176,7 +185,7 @@ struct rdh_ctx {
     bool movedSinceRender = false;  // prevTris holds positions that differ from ds.tris; set by the first update after a render
 
     // rdh_scene_rebuild_lights / rdh_build_alias_table_device (kernels_lights.h)
-    void *lightScratch = nullptr;    // powers + AliasWork for the scene's lightSamplerLength (scene allocation, made by the first rebuild)
+    void *lightScratch = nullptr;    // powers + AliasWork laid out for lightLenCap entries (scene allocation, made by the first rebuild)
     GrowBuf aliasScratch{bufs};      // values: the AliasWork of rdh_build_alias_table_device
     float *hLightSums = nullptr;     // pinned copy of a rebuild's {sum, 1 / sum}
     hipEvent_t evLights = nullptr;   // recorded after that copy
@@ -193,6 +202,21 @@ struct rdh_ctx {
     hipEvent_t evPoseStage[2] = {nullptr, nullptr};
     int poseStageNext = 0;
     GrowBuf dPoseStage{bufs};        // listed objects: where the kernel reads them
+
+    // rdh_scene_set_materials (kernels_materials.h).  The light count after an edit is a host sum over these copies.
+    std::vector<HostMaterial> hostMats;  // the scene's materials as they stand
+    std::vector<int> matPrims;           // per material: the triangles that carry it (from the upload's materialIds)
+    std::vector<unsigned> matStamp;      // per material: the edit that last listed it (duplicate check in O(count))
+    unsigned matEpoch = 0;
+    int numTextures = 0;                 // of the upload: what a map id may name
+    int lightCap = 0;                    // emitters that ds.lights, ds.lightPre and dLightPrims hold (scene allocations; never shrink)
+    int lightLenCap = 0;                 // entries that ds.lightAlias and lightScratch hold
+    bool listEdited = false;             // an edit rebuilt the list: emitScratch holds the device's own total (rdh_debug_read_lights)
+    GrowBuf hMatStage[2] = {GrowBuf{bufs, true}, GrowBuf{bufs, true}};  // listed materials: pinned {MatRec, id} of the last two edits
+    hipEvent_t evMatStage[2] = {nullptr, nullptr};
+    int matStageNext = 0;
+    GrowBuf dMatStage{bufs};             // listed materials: where k_mat_write reads them
+    GrowBuf emitScratch{bufs};           // 256-triangle blocks: the compaction's block totals, then {error flag, total}
 };
 
 namespace {
@@ -339,6 +363,18 @@ float asFloat(int32_t i) {
     memcpy(&f, &i, 4);
     return f;
 }
+
+MatRec toMatRec(const HostMaterial &m) {
+    MatRec r;
+    r.a = make_float4(asFloat(m.type), m.color[0], m.color[1], m.color[2]);
+    r.b = make_float4(m.metallic, m.roughness, m.ior, 0.f);
+    // Material field order: baseColorMapId, normalMapId, metallicMapId, roughnessMapId (src/material.h:282-285)
+    r.maps = make_int4(m.map[0], m.map[1], m.map[2], m.map[3]);
+    return r;
+}
+
+// A map id rdh_scene_upload accepts: baseColor (k == 0) may be procedural (-2); the others are -1 or a texture index.
+bool mapIdValid(int id, int k, int numTextures) { return id < numTextures && id >= (k == 0 ? -2 : -1); }
 
 // DScene::pairs (layouts.h) from the reference-layout arrays: the tree once, shared by the six orderings.  Returns false (no pairs;
 // the kernels then walk the six threaded arrays) unless bvhNodes[0..5] are six pre-orders of one binary tree over boundingBoxes —
@@ -891,6 +927,10 @@ int rdh_scene_free(rdh_ctx *c) {
     c->dLightPrims = nullptr;
     c->updPairs = nullptr;
     c->numLights = 0;
+    c->lightCap = c->lightLenCap = 0;
+    c->listEdited = false;
+    c->hostMats.clear();
+    c->matPrims.clear();
     c->prevTris = nullptr;  // tracking ends with the scene (its buffer was one of sceneAllocs)
     c->movedSinceRender = false;
     c->objects.clear();  // the object table, rest pose and world arrays were scene allocations too
@@ -919,6 +959,8 @@ void rdh_destroy(rdh_ctx *c) {
     for (hipEvent_t e : c->evAliasStage)
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->evPoseStage)
+        if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->evMatStage)
         if (e) hipEventDestroy(e);
     if (c->sideStream) hipStreamSynchronize(c->sideStream);
     if (c->litStream && c->litStream != c->sideStream) {
@@ -1010,20 +1052,15 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
     HIP_TRY(c, hipSetDevice(c->device));
     rdh_scene_free(c);
 
-    struct HostMaterial { int32_t type; float color[3]; float metallic, roughness, ior; int32_t map[4]; };
-    static_assert(sizeof(HostMaterial) == 44, "Material layout");
     const HostMaterial *hm = static_cast<const HostMaterial *>(d->materials);
     std::vector<MatRec> mats(d->numMaterials);
     for (int i = 0; i < d->numMaterials; i++) {
-        for (int k = 0; k < 4; k++) {  // baseColor may be procedural (-2); the others are -1 or a texture index
+        for (int k = 0; k < 4; k++) {
             int id = hm[i].map[k];
-            if (id >= d->numTextures || id < (k == 0 ? -2 : -1))
+            if (!mapIdValid(id, k, d->numTextures))
                 return fail(c, RDH_ERR_ARGS, "material %d: map id %d out of range (numTextures %d)", i, id, d->numTextures);
         }
-        mats[i].a = make_float4(asFloat(hm[i].type), hm[i].color[0], hm[i].color[1], hm[i].color[2]);
-        mats[i].b = make_float4(hm[i].metallic, hm[i].roughness, hm[i].ior, 0.f);
-        // Material field order: baseColorMapId, normalMapId, metallicMapId, roughnessMapId (src/material.h:282-285)
-        mats[i].maps = make_int4(hm[i].map[0], hm[i].map[1], hm[i].map[2], hm[i].map[3]);
+        mats[i] = toMatRec(hm[i]);
     }
     // textures: one blob + {width, height, first texel} per texture (src/scene.cpp:463-486)
     std::vector<float> texBlob;
@@ -1158,6 +1195,14 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
     c->ds.numPrims = N;
     c->ds.lightSamplerLength = d->lightSamplerLength;
     c->ds.sumLightPowerInv = d->sumLightPowerInv;
+    c->lightCap = d->numLights;
+    c->lightLenCap = d->lightSamplerLength;
+    c->hostMats.assign(hm, hm + d->numMaterials);  // rdh_scene_set_materials edits these and counts emitters from them
+    c->matPrims.assign((size_t)d->numMaterials, 0);
+    for (int p = 0; p < N; p++) c->matPrims[(size_t)d->materialIds[p]]++;
+    c->matStamp.assign((size_t)d->numMaterials, 0u);
+    c->matEpoch = 0;
+    c->numTextures = d->numTextures;
     c->haveScene = true;
     c->orderValid = false;
     return RDH_OK;
@@ -2609,7 +2654,7 @@ int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals,
         const dim3 grid((unsigned)((c->numLights + 255) / 256));
         if (c->lightsPending)  // a rebuild's value, not on the host yet: read it where the rebuild left it
             hipLaunchKernelGGL(k_light_precompute_dev, grid, dim3(256), 0, c->stream, c->ds.lights, const_cast<LightPre *>(c->ds.lightPre),
-                               c->numLights, (const float *)lightWork(c->lightScratch, c->ds.lightSamplerLength).sums + 1);
+                               c->numLights, (const float *)lightWork(c->lightScratch, c->lightLenCap).sums + 1);
         else
             hipLaunchKernelGGL(k_light_precompute, grid, dim3(256), 0, c->stream, c->ds.lights, const_cast<LightPre *>(c->ds.lightPre),
                                c->numLights, c->ds.sumLightPowerInv);
@@ -2891,6 +2936,24 @@ long long rdh_debug_read_tree(rdh_ctx *c, int which, void *hostOut, long long ma
 // ---- the light sampler on the device (kernels_lights.h) ---------------------------------------------------------------------------
 namespace {
 
+// The emitter compaction's workspace (kernels_materials.h): one total per 256-triangle block the buffer was grown for, then the
+// error flag and the grand total.
+struct EmitWork {
+    int *blockTotals, *err, *total;
+};
+EmitWork emitWork(const GrowBuf &b) {
+    int *p = b.as<int>();
+    return EmitWork{p, p + b.cap, p + b.cap + 1};
+}
+int growEmitWork(rdh_ctx *c, int numPrims, EmitWork *out) {
+    const size_t blocks = ((size_t)numPrims + 255) / 256;
+    const void *before = c->emitScratch.p;
+    if (int rc = grow(c, c->emitScratch, std::max<size_t>(blocks, 1), sizeof(int) * (std::max<size_t>(blocks, 1) + 2), Busy::Stream)) return rc;
+    if (c->emitScratch.p != before) c->listEdited = false;  // the last edit's total went with the old buffer
+    *out = emitWork(c->emitScratch);
+    return RDH_OK;
+}
+
 // values -> table, w.sums, on the context's stream.
 void launchAliasBuild(rdh_ctx *c, const float *d_values, int n, const AliasWork &w, AliasRec *d_table) {
     hipLaunchKernelGGL(k_alias_classify, dim3(1), dim3(64), 0, c->stream, d_values, n, w);
@@ -2932,13 +2995,13 @@ int rdh_scene_rebuild_lights(rdh_ctx *c, float envPower) {
     }
     if (!c->lightScratch) {
         void *p = nullptr;
-        HIP_TRY(c, hipMalloc(&p, aliasWorkBytes(len)));
+        HIP_TRY(c, hipMalloc(&p, aliasWorkBytes(c->lightLenCap)));
         c->sceneAllocs.push_back(p);
         c->lightScratch = p;
     }
     if ((rc = waitSideStreams(c))) return rc;  // the table and the per-light constants are rewritten in place
     float *power = static_cast<float *>(c->lightScratch);
-    const AliasWork w = lightWork(c->lightScratch, len);
+    const AliasWork w = lightWork(c->lightScratch, c->lightLenCap);  // laid out for the capacity (rdh_scene_set_materials changes len)
     hipLaunchKernelGGL(k_light_power, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights, c->numLights, len,
                        envPower, power);
     launchAliasBuild(c, power, len, w, const_cast<AliasRec *>(c->ds.lightAlias));
@@ -2960,13 +3023,21 @@ long long rdh_debug_read_lights(rdh_ctx *c, int which, void *hostOut, long long 
     if (which == 0) bytes = (long long)sizeof(AliasRec) * c->ds.lightSamplerLength;
     else if (which == 1) bytes = 16;
     else if (which == 2) bytes = (long long)sizeof(LightPre) * c->numLights;
+    else if (which == 4) bytes = (long long)sizeof(int32_t) * c->numLights;  // (3 stays refused)
     else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lights: which = %d", which);
     if (!hostOut) return bytes;
     if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lights: %lld bytes needed", bytes);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->listEdited && c->numLights > 0) {  // the compaction's own total against the host's sum (rdh_scene_set_materials)
+        int32_t total = 0;
+        HIP_TRY(c, hipMemcpy(&total, emitWork(c->emitScratch).total, sizeof(total), hipMemcpyDeviceToHost));
+        if (total != c->numLights)
+            return fail(c, RDH_ERR_STATE, "rdh_debug_read_lights: the device counted %d emitters, the host %d", total, c->numLights);
+    }
     if (which == 0 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.lightAlias, bytes, hipMemcpyDeviceToHost));
     else if (which == 2 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.lightPre, bytes, hipMemcpyDeviceToHost));
+    else if (which == 4 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->dLightPrims, bytes, hipMemcpyDeviceToHost));
     else if (which == 1) {
         const float f[2] = {1.f / c->ds.sumLightPowerInv, c->ds.sumLightPowerInv};
         const int32_t n[2] = {c->ds.lightSamplerLength, c->numLights};
@@ -3171,6 +3242,175 @@ int rdh_debug_read_world(rdh_ctx *c, float *verticesOut, float *normalsOut) {
     HIP_TRY(c, hipMemcpy(verticesOut, c->pose.worldVertices, bytes, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(normalsOut, c->pose.worldNormals, bytes, hipMemcpyDeviceToHost));
     return RDH_OK;
+}
+
+}  // extern "C"
+
+// ---- materials edited on the device (kernels_materials.h) -------------------------------------------------------------
+namespace {
+
+// A scene allocation replaced by one of `bytes`; the caller has made sure nothing still reads the old one.
+template <typename T>
+int replaceSceneAlloc(rdh_ctx *c, T **slot, size_t bytes) {
+    void *p = nullptr;
+    HIP_TRY(c, hipMalloc(&p, std::max<size_t>(bytes, 64)));
+    auto it = std::find(c->sceneAllocs.begin(), c->sceneAllocs.end(), static_cast<const void *>(*slot));
+    if (it != c->sceneAllocs.end()) {
+        hipFree(*it);
+        *it = p;
+    } else {
+        c->sceneAllocs.push_back(p);
+    }
+    *slot = static_cast<T *>(p);
+    return RDH_OK;
+}
+
+// Room for numLights emitters and a sampler of len entries.  Exceeding what the scene holds reallocates, which waits for every
+// stream that reads the old arrays; their contents are not kept (the caller rewrites all of them).  Shrinking frees nothing.
+int growLightArrays(rdh_ctx *c, int numLights, int len) {
+    if (numLights <= c->lightCap && len <= c->lightLenCap) return RDH_OK;
+    if (int rc = waitSideStreams(c)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (numLights > c->lightCap) {
+        LightRec *lights = const_cast<LightRec *>(c->ds.lights);
+        LightPre *pre = const_cast<LightPre *>(c->ds.lightPre);
+        if (int rc = replaceSceneAlloc(c, &lights, sizeof(LightRec) * (size_t)numLights)) return rc;
+        c->ds.lights = lights;
+        if (int rc = replaceSceneAlloc(c, &pre, sizeof(LightPre) * (size_t)numLights)) return rc;
+        c->ds.lightPre = pre;
+        if (int rc = replaceSceneAlloc(c, &c->dLightPrims, sizeof(int) * (size_t)numLights)) return rc;
+        c->lightCap = numLights;
+    }
+    if (len > c->lightLenCap) {
+        AliasRec *alias = const_cast<AliasRec *>(c->ds.lightAlias);
+        if (int rc = replaceSceneAlloc(c, &alias, sizeof(AliasRec) * (size_t)len)) return rc;
+        c->ds.lightAlias = alias;
+        if (c->lightScratch)  // (a scene that was never rebuilt gets its scratch from the first rebuild, at the capacity of then)
+            if (int rc = replaceSceneAlloc(c, &c->lightScratch, aliasWorkBytes(len))) return rc;
+        c->lightLenCap = len;
+    }
+    return RDH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_build_light_list_device(rdh_ctx *c, const float *d_vertices, const int32_t *d_materialIds, int32_t numPrims,
+                                const void *d_materials, int32_t numMaterials, int32_t *d_lightPrimIds, float *d_lightUnitRadiance,
+                                float *d_lightPower, int32_t *d_count) {
+    if (!c) return RDH_ERR_ARGS;
+    if (numPrims < 0 || numMaterials < 0 || !d_count ||
+        (numPrims > 0 && (!d_vertices || !d_materialIds || !d_materials || !d_lightPrimIds || !d_lightUnitRadiance || !d_lightPower)))
+        return fail(c, RDH_ERR_ARGS, "rdh_build_light_list_device: bad arguments");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (numPrims == 0) {
+        HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(int32_t), c->stream));
+        return RDH_OK;
+    }
+    EmitWork w{};
+    if (int rc = growEmitWork(c, numPrims, &w)) return rc;
+    const unsigned blocks = (unsigned)((numPrims + 255) / 256);
+    const RefEmitters ld{d_vertices, d_materialIds, static_cast<const RefMaterial *>(d_materials), numMaterials,
+                         d_lightPrimIds, d_lightUnitRadiance, d_lightPower, w.err};
+    HIP_TRY(c, hipMemsetAsync(w.err, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_emit_count_ref, dim3(blocks), dim3(256), 0, c->stream, ld, numPrims, w.blockTotals);
+    hipLaunchKernelGGL(k_emit_scan, dim3(1), dim3(256), 0, c->stream, w.blockTotals, (int)blocks, (const int *)w.err, d_count);
+    hipLaunchKernelGGL(k_emit_scatter_ref, dim3(blocks), dim3(256), 0, c->stream, ld, numPrims, (const int *)w.blockTotals);
+    HIP_TRY(c, hipGetLastError());
+    return RDH_OK;
+}
+
+int rdh_scene_set_materials(rdh_ctx *c, const int32_t *materialIds, const void *materials, int32_t count, float envPower) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_materials: no scene uploaded");
+    if (count < 0 || (count > 0 && (!materialIds || !materials))) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: bad arguments");
+    const bool hasEnv = c->ds.envTex >= 0;
+    if (hasEnv && !(envPower >= 0.f && envPower <= FLT_MAX))  // as rdh_scene_rebuild_lights
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: envPower %g must be finite and not negative", (double)envPower);
+    if (count == 0) return RDH_OK;
+    const HostMaterial *hm = static_cast<const HostMaterial *>(materials);
+    const int numMaterials = (int)c->hostMats.size();
+    if (++c->matEpoch == 0) {  // the stamps have wrapped
+        std::fill(c->matStamp.begin(), c->matStamp.end(), 0u);
+        c->matEpoch = 1;
+    }
+    bool relist = false;  // the set of Light materials, or a Light's colour, changes: the list and its LightRecs are derived again
+    for (int j = 0; j < count; j++) {
+        const int id = materialIds[j];
+        if (id < 0 || id >= numMaterials) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: material id %d of %d", id, numMaterials);
+        if (c->matStamp[(size_t)id] == c->matEpoch) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: material %d is listed twice", id);
+        c->matStamp[(size_t)id] = c->matEpoch;
+        for (int k = 0; k < 4; k++)
+            if (!mapIdValid(hm[j].map[k], k, c->numTextures))
+                return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: material %d: map id %d out of range (numTextures %d)", id,
+                            hm[j].map[k], c->numTextures);
+        const HostMaterial &old = c->hostMats[(size_t)id];
+        const bool was = old.type == kMaterialLight, is = hm[j].type == kMaterialLight;
+        if (was != is || (is && memcmp(old.color, hm[j].color, sizeof(old.color)) != 0)) relist = true;
+    }
+    int numLights = c->numLights;
+    if (relist) {  // the count after the edit, without the device: a host sum over the materials as they will stand
+        long long n = 0;
+        for (int i = 0; i < numMaterials; i++)
+            if (c->hostMats[(size_t)i].type == kMaterialLight && c->matStamp[(size_t)i] != c->matEpoch) n += c->matPrims[(size_t)i];
+        for (int j = 0; j < count; j++)
+            if (hm[j].type == kMaterialLight) n += c->matPrims[(size_t)materialIds[j]];
+        numLights = (int)n;
+    }
+    const int len = numLights + (hasEnv ? 1 : 0);
+    const int N = c->ds.numPrims;
+
+    // everything that can fail for want of memory comes before the scene is touched
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensureTreeHeader(c);
+    if (rc) return rc;
+    if (!c->evMatStage[0])
+        for (int k = 0; k < 2; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->evMatStage[k], hipEventDisableTiming));
+    const int s = c->matStageNext;
+    const size_t stageBytes = (sizeof(MatRec) + sizeof(int)) * (size_t)count;
+    HIP_TRY(c, hipEventSynchronize(c->evMatStage[s]));  // the copy of two edits ago (long done, normally)
+    if ((rc = grow(c, c->hMatStage[s], (size_t)count, stageBytes, Busy::Nothing))) return rc;
+    if ((rc = grow(c, c->dMatStage, (size_t)count, stageBytes, Busy::Stream))) return rc;
+    EmitWork w{};
+    if ((rc = growEmitWork(c, N, &w))) return rc;
+    if (relist && (rc = growLightArrays(c, numLights, len))) return rc;
+    c->matStageNext ^= 1;
+
+    MatRec *hRecs = c->hMatStage[s].as<MatRec>();
+    int *hIds = reinterpret_cast<int *>(hRecs + count);
+    for (int j = 0; j < count; j++) {
+        hRecs[j] = toMatRec(hm[j]);
+        hIds[j] = materialIds[j];
+        c->hostMats[(size_t)materialIds[j]] = hm[j];
+    }
+    if ((rc = waitSideStreams(c))) return rc;  // the records are rewritten in place
+    HIP_TRY(c, hipMemcpyAsync(c->dMatStage.p, c->hMatStage[s].p, stageBytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evMatStage[s], c->stream));
+    const MatRec *dRecs = c->dMatStage.as<MatRec>();
+    hipLaunchKernelGGL(k_mat_write, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, dRecs,
+                       reinterpret_cast<const int *>(dRecs + count), count, const_cast<MatRec *>(c->ds.mats));
+    const unsigned blocks = (unsigned)((N + 255) / 256);
+    const SceneEmitters ld{c->ds.tris, c->ds.mats, const_cast<unsigned char *>(c->ds.primClass), c->dLightPrims,
+                           const_cast<LightRec *>(c->ds.lights), numLights};
+    hipLaunchKernelGGL(k_emit_count_scene, dim3(blocks), dim3(256), 0, c->stream, ld, N, w.blockTotals);  // primClass rides here
+    HIP_TRY(c, hipGetLastError());
+    if (!relist) return RDH_OK;
+
+    c->numLights = numLights;
+    c->ds.lightSamplerLength = len;  // at once: the length never waits for the device
+    if (numLights > 0) {
+        hipLaunchKernelGGL(k_emit_scan, dim3(1), dim3(256), 0, c->stream, w.blockTotals, (int)blocks, (const int *)nullptr, w.total);
+        hipLaunchKernelGGL(k_emit_scatter_scene, dim3(blocks), dim3(256), 0, c->stream, ld, N, (const int *)w.blockTotals);
+        HIP_TRY(c, hipGetLastError());
+        c->listEdited = true;
+    }
+    if (len == 0) {  // nothing to sample: what an upload of a scene without lights holds; a rebuild still in flight is dropped
+        c->ds.sumLightPowerInv = 0.f;
+        c->lightsPending = false;
+        return RDH_OK;
+    }
+    return rdh_scene_rebuild_lights(c, envPower);
 }
 
 }  // extern "C"
