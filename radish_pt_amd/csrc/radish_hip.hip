@@ -77,11 +77,85 @@ struct HostMaterial {  // Material (src/material.h:276-286), as rdh_scene_desc::
 };
 static_assert(sizeof(HostMaterial) == 44, "Material layout");
 
+// A host array on its way to the device without a host wait: two pinned buffers used in turn, so that a call fills one while the
+// copy of the call before may still read the other (stageTake, stageSend below).
+struct StagePair {
+    GrowBuf buf[2];
+    hipEvent_t done[2] = {nullptr, nullptr};  // recorded after each buffer's last copy
+    int next = 0;
+    explicit StagePair(std::vector<GrowBuf *> &registry) : buf{GrowBuf{registry, true}, GrowBuf{registry, true}} {}
+};
+
+// Which ids a call has listed, in O(listed): an id is marked while its stamp is the call's epoch.
+struct StampSet {
+    std::vector<unsigned> stamp;
+    unsigned epoch = 0;
+    void reset(size_t n) {
+        stamp.assign(n, 0u);
+        epoch = 0;
+    }
+    void beginCall() {
+        if (++epoch == 0) {  // the stamps have wrapped
+            std::fill(stamp.begin(), stamp.end(), 0u);
+            epoch = 1;
+        }
+    }
+    bool marked(size_t id) const { return stamp[id] == epoch; }
+    bool mark(size_t id) {  // false: this call had marked it already
+        if (marked(id)) return false;
+        stamp[id] = epoch;
+        return true;
+    }
+};
+
+// Everything that lives and dies with the uploaded scene.  rdh_scene_free frees sceneAllocs and assigns a default-constructed
+// SceneState: a field added here needs no line anywhere else.  The device pointers below and in ds are all entries of sceneAllocs
+// (sceneAlloc / sceneReplace / sceneRelease).  What outlives a scene (workspaces, staging buffers, events) is rdh_ctx's.
+struct SceneState {
+    bool haveScene = false;
+    DScene ds{};  // all zero without a scene: every reader tests haveScene first
+    std::vector<void *> sceneAllocs;
+
+    // rdh_scene_update_geometry
+    int *dLightPrims = nullptr;      // the scene's current lightPrimIds (rdh_scene_set_materials rewrites it)
+    int numLights = 0;
+    PairRec *updPairs = nullptr;     // pairs of an updated tree when the upload had none
+    bool treePending = false;        // an update's header has not been folded into ds yet (settleTree)
+
+    // rdh_scene_refit_geometry (kernels_refit.h)
+    bool planValid = false;  // the refit plan in refitBuf is this topology's: built by the first refit after an upload / update_geometry
+    bool treeRefit = false;  // the pending tree header (treePending) is a refit's: only the root box changes
+
+    // rdh_scene_track_motion: the triangle records as this context's most recent rdh_gbuffer_render saw them
+    TriRec *prevTris = nullptr;
+    bool movedSinceRender = false;  // prevTris holds positions that differ from ds.tris; set by the first update after a render
+
+    // rdh_scene_rebuild_lights (kernels_lights.h)
+    void *lightScratch = nullptr;    // powers + AliasWork laid out for lightLenCap entries (made by the first rebuild)
+    bool lightsPending = false;      // a rebuild's sumLightPowerInv has not been folded into ds yet (settleLights)
+
+    // rdh_scene_set_objects / rdh_scene_pose_objects (kernels_pose.h)
+    std::vector<rdh_object_range> objects;  // host copy of the table, for the checks (empty: no table)
+    StampSet posed;                  // the objects a pose call lists (duplicate check)
+    PoseArgs pose{};                 // objects, rest pose and world arrays; the staged fields are filled in per call
+    bool worldStale = false;         // the world arrays are not what the records hold: the next pose seeds them again (k_pose_seed)
+
+    // rdh_scene_set_materials (kernels_materials.h; DESIGN 11g).  The light count after an edit is a host sum over these copies.
+    std::vector<HostMaterial> hostMats;  // the scene's materials as they stand
+    std::vector<int> matPrims;           // per material: the triangles that carry it (from the upload's materialIds)
+    StampSet edited;                     // the materials an edit lists (duplicate check, and the emitter count)
+    int numTextures = 0;                 // of the upload: what a map id may name
+    int lightCap = 0;                    // emitters that ds.lights, ds.lightPre and dLightPrims hold (never shrink)
+    int lightLenCap = 0;                 // entries that ds.lightAlias and lightScratch hold
+    bool listEdited = false;             // an edit rebuilt the list: emitScratch holds the device's own total (rdh_debug_read_lights)
+};
+
 struct rdh_ctx {
     int device = 0;
     int cus = 0;  // compute units of the device, asked for by the first launch that sizes a grid by them (cuCount)
     std::vector<std::pair<const void *, unsigned>> residentGrids;  // kernel -> workgroups of it the device keeps resident (residentGrid)
     std::vector<GrowBuf *> bufs;  // every GrowBuf below
+    std::vector<hipEvent_t> events;  // every event below (newEvent); rdh_destroy walks both
     hipStream_t ownStream = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t evStart = nullptr, evStop = nullptr;
@@ -94,10 +168,7 @@ struct rdh_ctx {
     bool timed = false;
     std::string err;
 
-    // scene
-    bool haveScene = false;
-    DScene ds{};
-    std::vector<void *> sceneAllocs;
+    SceneState scene;  // the uploaded scene and everything the edit entries hang on it
     Counters *dCounters = nullptr;
     PersistCounters *dPersist = nullptr;
     GrowBuf treeOvf{bufs};  // ints: the pair walkers' stacks beyond their LDS rings (traverse.h, pairPush), ray-batch and persistent kernels
@@ -107,9 +178,9 @@ struct rdh_ctx {
     // Longest-paths-first block order (k_persist_schedule), off the critical path: launch n writes blockCost[n & 1]; the
     // schedule of those costs runs on sideStream while launch n + 1 renders, and launch n + 2 reads its order from
     // blockOrder[n & 1] (and reuses the cost buffer the schedule has zeroed).
-    unsigned *blockCost[2] = {nullptr, nullptr};
-    unsigned *blockEma = nullptr;   // running mean of the costs over the launches so far
-    int *blockOrder[2] = {nullptr, nullptr};
+    GrowBuf blockCost[2] = {GrowBuf{bufs}, GrowBuf{bufs}};   // blocks (unsigned), as are the next two
+    GrowBuf blockEma{bufs};         // running mean of the costs over the launches so far
+    GrowBuf blockOrder[2] = {GrowBuf{bufs}, GrowBuf{bufs}};  // (int)
     int costBlocks = 0;             // blocks the arrays are sized for
     bool orderValid = false;        // false: restart the sequence (scene, camera size or partition changed)
     int persistFrame = 0;           // persistent launches since the last restart
@@ -131,7 +202,6 @@ struct rdh_ctx {
     // per-slot scratch of the split pass 1 (kernels_restir.h RestirSplit), grown on demand
     GrowBuf splitBuf{bufs};        // slots (splitLayout)
     long long splitLastSlots = 0;  // slots (= plane stride) of the last split pass 1: what rdh_restir_read_scratch reads back
-    LightPre *lightPre = nullptr;
     bool restirFirstFrame = true;
 
     // per-launch timing of the dominant (traversal) kernel: ring of hipEvent pairs (RDH_PT_PROFILE)
@@ -163,58 +233,25 @@ struct rdh_ctx {
     GrowBuf bvhScratch{bufs};        // primitives: the BvhWork buffers, one allocation
     GrowBuf lbvhScratch{bufs};       // primitives: the LbvhWork buffers and the BvhWork slot arrays (RDH_BVH_LBVH)
     GrowBuf updTree{bufs};           // primitives: the update's boxes + six int[S][3] orderings
-    int *dLightPrims = nullptr;      // the scene's current lightPrimIds (scene allocation; rdh_scene_set_materials rewrites it)
-    int numLights = 0;
-    PairRec *updPairs = nullptr;     // pairs of an updated tree when the upload had none (scene allocation)
-    int4 *dTreeHdr = nullptr;        // k_bvh_pairs' header: {treeDepth, error}, rootLo, rootHi
-    int4 *hTreeHdr = nullptr;        // its pinned host copy
+    GrowBuf dTreeHdr{bufs};          // three int4: k_bvh_pairs' header {treeDepth, error}, rootLo, rootHi
+    GrowBuf hTreeHdr{bufs, true};    // its pinned host copy
     hipEvent_t evTree = nullptr;     // recorded after that copy
-    bool treePending = false;        // an update's header has not been folded into ds yet (settleTree)
-    GrowBuf hAliasStage[2] = {GrowBuf{bufs, true}, GrowBuf{bufs, true}};  // records: pinned staging of the light tables of the last two updates
-    hipEvent_t evAliasStage[2] = {nullptr, nullptr};
-    int aliasStageNext = 0;
+    StagePair aliasStage{bufs};      // records: the caller's light table of an update
     hipEvent_t evUpdWait = nullptr;
 
-    // rdh_scene_refit_geometry (kernels_refit.h): the refit plan of the current topology and its workspace
-    GrowBuf refitBuf{bufs};  // primitives
-    bool planValid = false;  // built by the first refit after an upload / update_geometry; dropped by those and rdh_scene_free
-    bool treeRefit = false;  // the pending tree header (treePending) is a refit's: only the root box changes
-
-    // rdh_scene_track_motion: the triangle records as this context's most recent rdh_gbuffer_render saw them (scene allocation)
-    TriRec *prevTris = nullptr;
-    bool movedSinceRender = false;  // prevTris holds positions that differ from ds.tris; set by the first update after a render
+    GrowBuf refitBuf{bufs};  // primitives: the refit plan of the current topology and its workspace (rdh_scene_refit_geometry)
 
     // rdh_scene_rebuild_lights / rdh_build_alias_table_device (kernels_lights.h)
-    void *lightScratch = nullptr;    // powers + AliasWork laid out for lightLenCap entries (scene allocation, made by the first rebuild)
     GrowBuf aliasScratch{bufs};      // values: the AliasWork of rdh_build_alias_table_device
-    float *hLightSums = nullptr;     // pinned copy of a rebuild's {sum, 1 / sum}
+    GrowBuf hLightSums{bufs, true};  // two floats: pinned copy of a rebuild's {sum, 1 / sum}
     hipEvent_t evLights = nullptr;   // recorded after that copy
-    bool lightsPending = false;      // a rebuild's sumLightPowerInv has not been folded into ds yet (settleLights)
 
-    // rdh_scene_set_objects / rdh_scene_pose_objects (kernels_pose.h).  The table, the rest pose and the world arrays are scene
-    // allocations; the staging buffers are the context's.
-    std::vector<rdh_object_range> objects;  // host copy of the table, for the checks (empty: no table)
-    std::vector<unsigned> objectStamp;      // per object: the pose call that last listed it (duplicate check in O(count))
-    unsigned poseEpoch = 0;
-    PoseArgs pose{};                 // objects, rest pose and world arrays; the staged fields are filled in per call
-    bool worldStale = false;         // the world arrays are not what the records hold: the next pose seeds them again (k_pose_seed)
-    GrowBuf hPoseStage[2] = {GrowBuf{bufs, true}, GrowBuf{bufs, true}};  // listed objects: pinned {prefix, ids, xforms} of the last two poses
-    hipEvent_t evPoseStage[2] = {nullptr, nullptr};
-    int poseStageNext = 0;
+    // rdh_scene_pose_objects (kernels_pose.h): {prefix, ids, xforms} of the listed objects
+    StagePair poseStage{bufs};
     GrowBuf dPoseStage{bufs};        // listed objects: where the kernel reads them
 
-    // rdh_scene_set_materials (kernels_materials.h; DESIGN 11g).  The light count after an edit is a host sum over these copies.
-    std::vector<HostMaterial> hostMats;  // the scene's materials as they stand
-    std::vector<int> matPrims;           // per material: the triangles that carry it (from the upload's materialIds)
-    std::vector<unsigned> matStamp;      // per material: the edit that last listed it (duplicate check in O(count))
-    unsigned matEpoch = 0;
-    int numTextures = 0;                 // of the upload: what a map id may name
-    int lightCap = 0;                    // emitters that ds.lights, ds.lightPre and dLightPrims hold (scene allocations; never shrink)
-    int lightLenCap = 0;                 // entries that ds.lightAlias and lightScratch hold
-    bool listEdited = false;             // an edit rebuilt the list: emitScratch holds the device's own total (rdh_debug_read_lights)
-    GrowBuf hMatStage[2] = {GrowBuf{bufs, true}, GrowBuf{bufs, true}};  // listed materials: pinned {MatRec, id} of the last two edits
-    hipEvent_t evMatStage[2] = {nullptr, nullptr};
-    int matStageNext = 0;
+    // rdh_scene_set_materials (kernels_materials.h): {MatRec, id} of the listed materials
+    StagePair matStage{bufs};
     GrowBuf dMatStage{bufs};             // listed materials: where k_mat_write reads them
     GrowBuf emitScratch{bufs};           // 256-triangle blocks: the compaction's block totals, then {error flag, total}
 };
@@ -347,14 +384,81 @@ int growCarved(rdh_ctx *c, GrowBuf &b, size_t need, Busy busy, F layout) {
     return RDH_OK;
 }
 
+// Every event of a context is made here and dies in rdh_destroy's walk of rdh_ctx::events.
+int newEvent(rdh_ctx *c, hipEvent_t *out, bool timing = false) {
+    HIP_TRY(c, timing ? hipEventCreate(out) : hipEventCreateWithFlags(out, hipEventDisableTiming));
+    c->events.push_back(*out);
+    return RDH_OK;
+}
+
+// StagePair: the host side of the next upload, made to hold `need` units in `bytes` bytes.  Waits only for this buffer's previous
+// copy, that of two calls ago (long done, normally).
+template <typename T>
+int stageTake(rdh_ctx *c, StagePair &s, size_t need, size_t bytes, T **host) {
+    for (hipEvent_t &e : s.done)
+        if (!e)
+            if (int rc = newEvent(c, &e)) return rc;
+    HIP_TRY(c, hipEventSynchronize(s.done[s.next]));
+    if (int rc = grow(c, s.buf[s.next], need, bytes, Busy::Nothing)) return rc;  // (the event above: its last copy is done)
+    *host = s.buf[s.next].as<T>();
+    return RDH_OK;
+}
+// ... and its way to `dst` on the render stream.  The pair turns to its other buffer only here: a call that fails between
+// stageTake and stageSend leaves this one to the next call.
+int stageSend(rdh_ctx *c, StagePair &s, void *dst, size_t bytes) {
+    HIP_TRY(c, hipMemcpyAsync(dst, s.buf[s.next].p, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(s.done[s.next], c->stream));
+    s.next ^= 1;
+    return RDH_OK;
+}
+
+// The scene's device allocations (SceneState::sceneAllocs): made, replaced and freed here and nowhere else, at least
+// kMinSceneAlloc bytes each so that an empty array still has an address.  rdh_scene_free frees what is left.
+constexpr size_t kMinSceneAlloc = 64;
+template <typename T>
+int sceneAlloc(rdh_ctx *c, T **slot, size_t bytes) {
+    void *p = nullptr;
+    HIP_TRY(c, hipMalloc(&p, std::max(bytes, kMinSceneAlloc)));
+    c->scene.sceneAllocs.push_back(p);
+    *slot = static_cast<T *>(p);
+    return RDH_OK;
+}
+// Frees *slot (null, or not the scene's: nothing to free) and clears it; the caller has made sure nothing still reads it.
+// `quiet`, for a replacement and for the way out of a failed call: hipFree's answer is dropped, so the text of the failure that
+// the caller reports stays in c->err.
+template <typename T>
+int sceneRelease(rdh_ctx *c, T **slot, bool quiet = false) {
+    void *p = const_cast<void *>(static_cast<const void *>(*slot));
+    *slot = nullptr;
+    auto &allocs = c->scene.sceneAllocs;
+    const auto it = std::find(allocs.begin(), allocs.end(), p);
+    if (it == allocs.end()) return RDH_OK;
+    allocs.erase(it);
+    if (quiet) hipFree(p);
+    else HIP_TRY(c, hipFree(p));
+    return RDH_OK;
+}
+// *slot replaced by an allocation of `bytes` (contents are not kept); a failure leaves the old one in place.
+template <typename T>
+int sceneReplace(rdh_ctx *c, T **slot, size_t bytes) {
+    T *fresh = nullptr;
+    if (int rc = sceneAlloc(c, &fresh, bytes)) return rc;
+    sceneRelease(c, slot, true);
+    *slot = fresh;
+    return RDH_OK;
+}
+
 template <typename T>
 int uploadVec(rdh_ctx *c, const std::vector<T> &v, const T **out) {
-    void *p = nullptr;
-    size_t bytes = std::max<size_t>(v.size() * sizeof(T), 16);
-    HIP_TRY(c, hipMalloc(&p, bytes));
-    c->sceneAllocs.push_back(p);
-    if (!v.empty()) HIP_TRY(c, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T *>(p);
+    if (int rc = sceneAlloc(c, out, v.size() * sizeof(T))) return rc;
+    if (!v.empty()) HIP_TRY(c, hipMemcpy(const_cast<T *>(*out), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return RDH_OK;
+}
+
+// What rdh_scene_rebuild_lights, rdh_scene_pose_objects and rdh_scene_set_materials ask of the environment entry's power.
+int checkEnvPower(rdh_ctx *c, const char *what, float envPower) {
+    if (c->scene.ds.envTex >= 0 && !(envPower >= 0.f && envPower <= FLT_MAX))
+        return fail(c, RDH_ERR_ARGS, "%s: envPower %g must be finite and not negative", what, (double)envPower);
     return RDH_OK;
 }
 
@@ -531,10 +635,10 @@ PixelMap makePixelMap(const rdh_ctx *c) {
 // (a sixth of the node footprint, half the dependent round trips).  RDH_PT_NO_PAIRS / RADISH_PAIRS=0 keep the threaded walks.
 constexpr int kPairMinNodes = 0;
 bool usePairs(const rdh_ctx *c, uint32_t flags) {
-    if (!c->ds.pairs || (flags & RDH_PT_NO_PAIRS)) return false;
+    if (!c->scene.ds.pairs || (flags & RDH_PT_NO_PAIRS)) return false;
     if (flags & RDH_PT_PAIRS) return true;
     if (c->pairMode >= 0) return c->pairMode != 0;
-    return c->ds.bvhSize >= kPairMinNodes;
+    return c->scene.ds.bvhSize >= kPairMinNodes;
 }
 
 // Primary rays as wave packets (traverse.h, packetWalk)?  RADISH_PACKETS=0 in the environment switches them off (experiments).
@@ -554,34 +658,34 @@ unsigned gridBlocks(const PixelMap &pm) { return (((unsigned)pm.numBlocks + 7u) 
 // Fold the tree header of the last rdh_scene_update_geometry into ds (the kernels take treeDepth, the root box and whether pairs
 // exist as launch arguments): waits for that update's build, which the stream has to finish before the next launch anyway.
 int settleTree(rdh_ctx *c) {
-    if (!c->treePending) return RDH_OK;
+    if (!c->scene.treePending) return RDH_OK;
     HIP_TRY(c, hipEventSynchronize(c->evTree));
-    c->treePending = false;
-    if (c->treeRefit) {  // same topology: treeDepth, pairs and the root's w stay
-        c->treeRefit = false;
-        if (!c->ds.pairs) return RDH_OK;  // the root box is a pair walk's argument; without pairs the upload leaves it zero too
-        const int4 lo = c->hTreeHdr[1], hi = c->hTreeHdr[2];
-        c->ds.rootLo = make_float4(__builtin_bit_cast(float, lo.x), __builtin_bit_cast(float, lo.y), __builtin_bit_cast(float, lo.z), c->ds.rootLo.w);
-        c->ds.rootHi = make_float4(__builtin_bit_cast(float, hi.x), __builtin_bit_cast(float, hi.y), __builtin_bit_cast(float, hi.z), c->ds.rootHi.w);
+    c->scene.treePending = false;
+    if (c->scene.treeRefit) {  // same topology: treeDepth, pairs and the root's w stay
+        c->scene.treeRefit = false;
+        if (!c->scene.ds.pairs) return RDH_OK;  // the root box is a pair walk's argument; without pairs the upload leaves it zero too
+        const int4 lo = c->hTreeHdr.as<int4>()[1], hi = c->hTreeHdr.as<int4>()[2];
+        c->scene.ds.rootLo = make_float4(__builtin_bit_cast(float, lo.x), __builtin_bit_cast(float, lo.y), __builtin_bit_cast(float, lo.z), c->scene.ds.rootLo.w);
+        c->scene.ds.rootHi = make_float4(__builtin_bit_cast(float, hi.x), __builtin_bit_cast(float, hi.y), __builtin_bit_cast(float, hi.z), c->scene.ds.rootHi.w);
         return RDH_OK;
     }
-    const int4 h0 = c->hTreeHdr[0], lo = c->hTreeHdr[1], hi = c->hTreeHdr[2];
+    const int4 *hdr = c->hTreeHdr.as<int4>(), h0 = hdr[0], lo = hdr[1], hi = hdr[2];
     if (h0.y != 0) {
-        c->haveScene = false;
+        c->scene.haveScene = false;
         return fail(c, RDH_ERR_STATE, "device BVH build failed (error bits %d); the scene must be uploaded again", h0.y);
     }
     constexpr int kMaxPairDepth = 2048;  // as rdh_scene_upload
-    const PairRec *pairs = c->updPairs ? c->updPairs : c->ds.pairs;
+    const PairRec *pairs = c->scene.updPairs ? c->scene.updPairs : c->scene.ds.pairs;
     if (h0.x <= kMaxPairDepth) {
-        c->ds.pairs = pairs;
-        c->ds.treeDepth = h0.x;
-        c->ds.rootLo = make_float4(__builtin_bit_cast(float, lo.x), __builtin_bit_cast(float, lo.y), __builtin_bit_cast(float, lo.z),
+        c->scene.ds.pairs = pairs;
+        c->scene.ds.treeDepth = h0.x;
+        c->scene.ds.rootLo = make_float4(__builtin_bit_cast(float, lo.x), __builtin_bit_cast(float, lo.y), __builtin_bit_cast(float, lo.z),
                                    __builtin_bit_cast(float, lo.w));
-        c->ds.rootHi = make_float4(__builtin_bit_cast(float, hi.x), __builtin_bit_cast(float, hi.y), __builtin_bit_cast(float, hi.z),
+        c->scene.ds.rootHi = make_float4(__builtin_bit_cast(float, hi.x), __builtin_bit_cast(float, hi.y), __builtin_bit_cast(float, hi.z),
                                    __builtin_bit_cast(float, hi.w));
     } else {
-        c->ds.pairs = nullptr;
-        c->ds.treeDepth = 0;
+        c->scene.ds.pairs = nullptr;
+        c->scene.ds.treeDepth = 0;
     }
     return RDH_OK;
 }
@@ -590,21 +694,21 @@ int settleTree(rdh_ctx *c) {
 // settleTree folds the tree header: waits for that rebuild, which the stream has to finish before the next launch anyway.  A later
 // update that brought a host rdh_light_update has cleared lightsPending: its value stands.
 int settleLights(rdh_ctx *c) {
-    if (!c->lightsPending) return RDH_OK;
+    if (!c->scene.lightsPending) return RDH_OK;
     HIP_TRY(c, hipEventSynchronize(c->evLights));
-    c->lightsPending = false;
-    c->ds.sumLightPowerInv = c->hLightSums[1];
+    c->scene.lightsPending = false;
+    c->scene.ds.sumLightPowerInv = c->hLightSums.as<float>()[1];
     return RDH_OK;
 }
 
 int requireReady(rdh_ctx *c) {
     if (!c) return RDH_ERR_ARGS;
-    if (c->haveScene) {
+    if (c->scene.haveScene) {
         int rc = settleTree(c);
         if (rc) return rc;
         if ((rc = settleLights(c))) return rc;
     }
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded (rdh_scene_upload)");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded (rdh_scene_upload)");
     if (!c->haveCamera) return fail(c, RDH_ERR_NO_SCENE, "no camera set (rdh_set_camera)");
     return RDH_OK;
 }
@@ -616,7 +720,7 @@ long profBegin(rdh_ctx *c, uint32_t flags) {
     if (!(flags & RDH_PT_PROFILE) || c->profUsed >= kProfilePairs) return -1;
     if (c->profEvents.size() < 2 * (c->profUsed + 1)) {
         hipEvent_t a = nullptr, b = nullptr;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -1;
+        if (newEvent(c, &a, true) || newEvent(c, &b, true)) return -1;
         c->profEvents.push_back(a);
         c->profEvents.push_back(b);
     }
@@ -665,10 +769,10 @@ int wavefrontEnsure(rdh_ctx *c, const PixelMap &pm, int samples) {
         w.litCap = 0;
     }
     if (!c->evWfFork) {
-        HIP_TRY(c, hipEventCreateWithFlags(&c->evWfFork, hipEventDisableTiming));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->evWfJoin, hipEventDisableTiming));
+        int rc;
+        if ((rc = newEvent(c, &c->evWfFork)) || (rc = newEvent(c, &c->evWfJoin))) return rc;
         HIP_TRY(c, hipStreamCreateWithFlags(&c->wfStream, hipStreamNonBlocking));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->evWfJoin3, hipEventDisableTiming));
+        if ((rc = newEvent(c, &c->evWfJoin3))) return rc;
     }
     c->wfCapacity = slots;
     return RDH_OK;
@@ -705,7 +809,7 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
     int parts = ((flags & RDH_PT_WF_SUBFRAMES) && pm.numBlocks >= 2048) ? (partsEnv >= 1 && partsEnv <= kWfParts ? partsEnv : kWfPartsDefault) : 1;
     // the pair walkers' stacks beyond their LDS rings: a strip per logical wave of the (full) trace grid per pipeline.  Deep trees
     // stay one pipeline rather than hold more strip bytes than the single pipeline does (at depth 2 048 that is ~6 GB).
-    const int ovfDepth = c->ds.treeDepth + 1;  // entry numbers, not rows beyond the ring (traverse.h, pairPush)
+    const int ovfDepth = c->scene.ds.treeDepth + 1;  // entry numbers, not rows beyond the ring (traverse.h, pairPush)
     const size_t ovfNeed = (size_t)traceGrid * 4 * 64 * (size_t)ovfDepth * 2;  // int2 entries; by the launched grid here (kept as found)
     if (tree && parts > 1 && (size_t)parts * ovfNeed * sizeof(int) > kWfStripBudget) parts = 1;
     hipStream_t sts[kWfParts] = {c->stream, c->sideStream, c->wfStream};
@@ -739,7 +843,7 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
         const unsigned nLocal = (unsigned)(pm.numBlocks - h + parts - 1) / (unsigned)parts;
         const unsigned gridBlk = (((nLocal * (unsigned)samples + 3u) / 4u + 7u) / 8u) * 8u;
         keep(hipMemsetAsync(w.ctr, 0, sizeof(WaveCounters), st), "hipMemsetAsync(wavefront counters)");
-        hipLaunchKernelGGL(k_wf_raygen, dim3(gridBlk), dim3(256), 0, st, c->ds, c->cam, pm, w, looper, samples, h, parts);
+        hipLaunchKernelGGL(k_wf_raygen, dim3(gridBlk), dim3(256), 0, st, c->scene.ds, c->cam, pm, w, looper, samples, h, parts);
     }
     for (int k = 0; k <= maxDepth && rc == RDH_OK; k++) {
         for (int h = 0; h < parts; h++) {  // interleaved issue: stage k of every pipeline before stage k + 1 of any
@@ -747,10 +851,10 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
             WaveWorkspace &w = c->wf[h];
             long pe = (h == 0 && parts == 1) ? profBegin(c, flags) : -1;
             withBools([&](auto cnt, auto pr) {
-                hipLaunchKernelGGL((k_wf_trace<cnt.value, pr.value>), dim3(traceGrid), dim3(256), 0, st, c->ds, w, k);
+                hipLaunchKernelGGL((k_wf_trace<cnt.value, pr.value>), dim3(traceGrid), dim3(256), 0, st, c->scene.ds, w, k);
             }, count, tree);
             profEnd(c, pe);
-            hipLaunchKernelGGL(k_wf_shade, dim3(shadeGrid), dim3(256), 0, st, c->ds, w, k, maxDepth, sort ? 1 : 0);
+            hipLaunchKernelGGL(k_wf_shade, dim3(shadeGrid), dim3(256), 0, st, c->scene.ds, w, k, maxDepth, sort ? 1 : 0);
         }
         keep(hipGetLastError(), "wavefront stage launch");
     }
@@ -779,7 +883,7 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
 // The walkers' stacks beyond their LDS rings (traverse.h, pairPush): one allocation of the context, grown on demand, a strip per
 // lane of the UNDIVIDED resident grid `resident`, not of the context's share of it (kept as found).
 int ensureStackOverflow(rdh_ctx *c, unsigned resident) {
-    const size_t ints = (size_t)resident * 64 * (size_t)(c->ds.treeDepth + 1) * 2;  // int2 entries, by entry number (pairPush)
+    const size_t ints = (size_t)resident * 64 * (size_t)(c->scene.ds.treeDepth + 1) * 2;  // int2 entries, by entry number (pairPush)
     return grow(c, c->treeOvf, ints, ints * sizeof(int), Busy::Device);
 }
 
@@ -787,7 +891,7 @@ int ensureStackOverflow(rdh_ctx *c, unsigned resident) {
 uint32_t resolveStructure(const rdh_ctx *c, const PixelMap &pm, uint32_t flags) {
     if (!(flags & RDH_PT_AUTO)) return flags;
     flags &= ~(RDH_PT_AUTO | RDH_PT_WAVEFRONT | RDH_PT_SORT_MATERIAL | RDH_PT_WF_SUBFRAMES | RDH_PT_PERSISTENT);
-    const bool wavefront = c->ds.bvhSize >= 100000 && pm.numBlocks >= 12000;
+    const bool wavefront = c->scene.ds.bvhSize >= 100000 && pm.numBlocks >= 12000;
     return flags | (wavefront ? (RDH_PT_WAVEFRONT | RDH_PT_SORT_MATERIAL | RDH_PT_WF_SUBFRAMES) : RDH_PT_PERSISTENT);
 }
 
@@ -800,7 +904,7 @@ int launchWalk(rdh_ctx *c, const float *d_rays, long long n, int4 *d_hits, int *
                const int *deferList = nullptr, int slotList = 0, bool pairs = false, bool packets = false, int budget = kPacketBudget) {
     const bool any = d_occ != nullptr, defer = deferCount != nullptr;
     packets = packets && !any && n > 0 && (n + 255) / 256 <= 0x7fffffffll;  // closest hits of a list the caller calls coherent
-    if (pairs && !c->ds.pairs) return fail(c, RDH_ERR_UNSUPPORTED, "RDH_PT_PAIRS: the uploaded node arrays are not six orderings of one binary tree, or that tree is more than 2 048 levels deep");
+    if (pairs && !c->scene.ds.pairs) return fail(c, RDH_ERR_UNSUPPORTED, "RDH_PT_PAIRS: the uploaded node arrays are not six orderings of one binary tree, or that tree is more than 2 048 levels deep");
     unsigned resGrid = 0;
     int rc = RDH_OK;
     withBools([&](auto a) {
@@ -808,28 +912,28 @@ int launchWalk(rdh_ctx *c, const float *d_rays, long long n, int4 *d_hits, int *
     }, any);
     if (rc) return rc;
     const unsigned grid = sharedGrid(c, resGrid, (unsigned long long)((n + 63) / 64));  // work: 64-ray chunks
-    const int ovfDepth = c->ds.treeDepth + 1;  // entry numbers (traverse.h, pairPush)
+    const int ovfDepth = c->scene.ds.treeDepth + 1;  // entry numbers (traverse.h, pairPush)
     if (pairs && !packets && (rc = ensureStackOverflow(c, resGrid))) return rc;
     int2 *const ovf = c->treeOvf.as<int2>();
     if (!packets) HIP_TRY(c, hipMemsetAsync(c->dPersist, 0, offsetof(PersistCounters, deferred), c->stream));  // the walkers' chunk counter
     if (defer) {
         if ((rc = forkLiteral(c))) return rc;
         withBools([&](auto cnt, auto a) {
-            hipLaunchKernelGGL((k_trace_wg_list<cnt.value, a.value>), dim3(kWalkDeferCap), dim3(kWgTraceThreads), 0, c->litStream, c->ds, d_rays, deferList, deferCount, d_hits, d_occ);
+            hipLaunchKernelGGL((k_trace_wg_list<cnt.value, a.value>), dim3(kWalkDeferCap), dim3(kWgTraceThreads), 0, c->litStream, c->scene.ds, d_rays, deferList, deferCount, d_hits, d_occ);
         }, count, any);
     }
     if (packets) {  // one 64-ray chunk per wave, walked as a packet (kernels_walk.h, k_walk_packet)
         const unsigned pgrid = (unsigned)((n + 255) / 256);
         withBools([&](auto cnt, auto def) {
-            hipLaunchKernelGGL((k_walk_packet<cnt.value, def.value>), dim3(pgrid), dim3(256), 0, c->stream, c->ds, d_rays, n, d_hits, deferCount, slotList, budget);
+            hipLaunchKernelGGL((k_walk_packet<cnt.value, def.value>), dim3(pgrid), dim3(256), 0, c->stream, c->scene.ds, d_rays, n, d_hits, deferCount, slotList, budget);
         }, count, defer);
     } else {
         withBools([&](auto cnt, auto a, auto def) {
             if (pairs)
-                hipLaunchKernelGGL((k_walk_pair<cnt.value, a.value, def.value>), dim3(grid), dim3(64), 0, c->stream, c->ds, d_rays, n, d_hits, d_occ,
+                hipLaunchKernelGGL((k_walk_pair<cnt.value, a.value, def.value>), dim3(grid), dim3(64), 0, c->stream, c->scene.ds, d_rays, n, d_hits, d_occ,
                                    c->dPersist, ovf, ovfDepth, deferCount, slotList);
             else
-                hipLaunchKernelGGL((k_walk_persistent<cnt.value, a.value, def.value>), dim3(grid), dim3(64), 0, c->stream, c->ds, d_rays, n, d_hits, d_occ,
+                hipLaunchKernelGGL((k_walk_persistent<cnt.value, a.value, def.value>), dim3(grid), dim3(64), 0, c->stream, c->scene.ds, d_rays, n, d_hits, d_occ,
                                    c->dPersist, deferCount, slotList);
         }, count, any, defer);
     }
@@ -877,13 +981,10 @@ int rdh_create(rdh_ctx **out, int device) {
     rdh_ctx *c = new rdh_ctx;
     c->device = device;
     if (hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&c->evStart) != hipSuccess || hipEventCreate(&c->evStop) != hipSuccess ||
+        newEvent(c, &c->evStart, true) || newEvent(c, &c->evStop, true) ||
         hipStreamCreateWithFlags(&c->sideStream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evFrame, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evSched[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evSched[1], hipEventDisableTiming) != hipSuccess ||
+        newEvent(c, &c->evFork) || newEvent(c, &c->evJoin) || newEvent(c, &c->evFrame) || newEvent(c, &c->evSched[0]) ||
+        newEvent(c, &c->evSched[1]) ||
         hipMalloc((void **)&c->dCounters, sizeof(Counters)) != hipSuccess ||
         hipMalloc((void **)&c->dPersist, sizeof(PersistCounters)) != hipSuccess) {
         delete c;
@@ -916,83 +1017,28 @@ int rdh_scene_free(rdh_ctx *c) {
     if (!c) return RDH_ERR_ARGS;
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    for (void *p : c->sceneAllocs) hipFree(p);
-    c->sceneAllocs.clear();
-    c->haveScene = false;
-    c->treePending = false;
-    c->treeRefit = false;
-    c->planValid = false;
-    c->lightsPending = false;
-    c->lightScratch = nullptr;  // one of sceneAllocs
-    c->dLightPrims = nullptr;
-    c->updPairs = nullptr;
-    c->numLights = 0;
-    c->lightCap = c->lightLenCap = 0;
-    c->listEdited = false;
-    c->hostMats.clear();
-    c->matPrims.clear();
-    c->prevTris = nullptr;  // tracking ends with the scene (its buffer was one of sceneAllocs)
-    c->movedSinceRender = false;
-    c->objects.clear();  // the object table, rest pose and world arrays were scene allocations too
-    c->pose = PoseArgs{};
-    c->worldStale = false;
+    for (void *p : c->scene.sceneAllocs) hipFree(p);
+    c->scene = SceneState{};
     return RDH_OK;
 }
 
 void rdh_destroy(rdh_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
-    rdh_scene_free(c);
+    rdh_scene_free(c);  // drains the render stream
     rdh_restir_free(c);
     rdh_comm_destroy(c);
+    // every other stream is drained before the buffers and events its work may use go
+    for (hipStream_t s : {c->sideStream, c->litStream, c->wfStream, c->commStream})
+        if (s) hipStreamSynchronize(s);
     for (void *p : c->wfAllocs) hipFree(p);
-    for (hipEvent_t e : c->profEvents) hipEventDestroy(e);
     if (c->dCounters) hipFree(c->dCounters);
     if (c->dPersist) hipFree(c->dPersist);
     for (GrowBuf *b : c->bufs) b->release();
-    if (c->dTreeHdr) hipFree(c->dTreeHdr);
-    if (c->hTreeHdr) hipHostFree(c->hTreeHdr);
-    if (c->evTree) hipEventDestroy(c->evTree);
-    if (c->evUpdWait) hipEventDestroy(c->evUpdWait);
-    if (c->hLightSums) hipHostFree(c->hLightSums);
-    if (c->evLights) hipEventDestroy(c->evLights);
-    for (hipEvent_t e : c->evAliasStage)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->evPoseStage)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->evMatStage)
-        if (e) hipEventDestroy(e);
-    if (c->sideStream) hipStreamSynchronize(c->sideStream);
-    if (c->litStream && c->litStream != c->sideStream) {
-        hipStreamSynchronize(c->litStream);
-        hipStreamDestroy(c->litStream);
-    }
-    for (int k = 0; k < 2; k++) {
-        if (c->blockCost[k]) hipFree(c->blockCost[k]);
-        if (c->blockOrder[k]) hipFree(c->blockOrder[k]);
-        if (c->evSched[k]) hipEventDestroy(c->evSched[k]);
-    }
-    if (c->blockEma) hipFree(c->blockEma);
-    if (c->evFrame) hipEventDestroy(c->evFrame);
-    if (c->wfStream) {
-        hipStreamSynchronize(c->wfStream);
-        hipStreamDestroy(c->wfStream);
-    }
-    if (c->commStream) {
-        hipStreamSynchronize(c->commStream);
-        hipStreamDestroy(c->commStream);
-        for (hipEvent_t e : {c->evToComm, c->evGbuf, c->evImg, c->evResv})
-            if (e) hipEventDestroy(e);
-    }
-    if (c->evWfJoin3) hipEventDestroy(c->evWfJoin3);
-    if (c->evWfFork) hipEventDestroy(c->evWfFork);
-    if (c->evWfJoin) hipEventDestroy(c->evWfJoin);
-    if (c->evStart) hipEventDestroy(c->evStart);
-    if (c->evStop) hipEventDestroy(c->evStop);
-    if (c->evFork) hipEventDestroy(c->evFork);
-    if (c->evJoin) hipEventDestroy(c->evJoin);
-    if (c->sideStream) hipStreamDestroy(c->sideStream);
-    if (c->ownStream) hipStreamDestroy(c->ownStream);
+    for (hipEvent_t e : c->events) hipEventDestroy(e);
+    if (c->litStream && c->litStream != c->sideStream) hipStreamDestroy(c->litStream);
+    for (hipStream_t s : {c->wfStream, c->commStream, c->sideStream, c->ownStream})
+        if (s) hipStreamDestroy(s);
     delete c;
 }
 
@@ -1091,26 +1137,26 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
         attrs[p].d = make_float4(t[3], t[4], t[5], 0.f);
     }
     int rc;
-    if ((rc = uploadVec(c, tris, &c->ds.tris))) return rc;
-    if ((rc = uploadVec(c, attrs, &c->ds.attrs))) return rc;
-    if ((rc = uploadVec(c, mats, &c->ds.mats))) return rc;
+    if ((rc = uploadVec(c, tris, &c->scene.ds.tris))) return rc;
+    if ((rc = uploadVec(c, attrs, &c->scene.ds.attrs))) return rc;
+    if ((rc = uploadVec(c, mats, &c->scene.ds.mats))) return rc;
     {  // shading class per triangle (Material::Type of its material, src/material.h:129): the key of the wavefront material sort
         std::vector<unsigned char> cls(N);
         for (int p = 0; p < N; p++) {
             const int type = hm[d->materialIds[p]].type;
             cls[p] = type == 0 ? 1 : (type == 1 ? 2 : (type == 2 ? 3 : 0));  // Lambertian, MetallicWorkflow, Dielectric; else terminal
         }
-        if ((rc = uploadVec(c, cls, &c->ds.primClass))) return rc;
+        if ((rc = uploadVec(c, cls, &c->scene.ds.primClass))) return rc;
     }
-    if ((rc = uploadVec(c, texBlob, &c->ds.texData))) return rc;
-    if ((rc = uploadVec(c, texInfo, &c->ds.texInfo))) return rc;
+    if ((rc = uploadVec(c, texBlob, &c->scene.ds.texData))) return rc;
+    if ((rc = uploadVec(c, texInfo, &c->scene.ds.texInfo))) return rc;
     std::vector<AliasRec> envAlias(d->envMapSamplerLength);
     if (d->envMapSamplerLength) memcpy(envAlias.data(), d->envMapSampler, sizeof(AliasRec) * envAlias.size());
     for (auto &e : envAlias)
         if (e.failId < 0 || e.failId >= d->envMapSamplerLength) return fail(c, RDH_ERR_ARGS, "env-map alias table failId out of range");
-    if ((rc = uploadVec(c, envAlias, &c->ds.envAlias))) return rc;
-    c->ds.envTex = d->envMapTexId;
-    c->ds.envSamplerLength = d->envMapSamplerLength;
+    if ((rc = uploadVec(c, envAlias, &c->scene.ds.envAlias))) return rc;
+    c->scene.ds.envTex = d->envMapTexId;
+    c->scene.ds.envSamplerLength = d->envMapSamplerLength;
 
     // The six orderings live in ONE allocation, (S + 1) records each (+1: a readable pad record at index S for speculative
     // next-node loads), so that a kernel can address any record as base + 32-bit byte offset (saddr form, one VALU) instead
@@ -1133,23 +1179,23 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
         dst[S].lo_prim = make_float4(0.f, 0.f, 0.f, asFloat(-1));
         dst[S].hi_next = make_float4(0.f, 0.f, 0.f, asFloat(S));
     }
-    if ((rc = uploadVec(c, nodes, &c->ds.nodes[0]))) return rc;
-    for (int k = 1; k < 6; k++) c->ds.nodes[k] = c->ds.nodes[0] + (size_t)k * (S + 1);
+    if ((rc = uploadVec(c, nodes, &c->scene.ds.nodes[0]))) return rc;
+    for (int k = 1; k < 6; k++) c->scene.ds.nodes[k] = c->scene.ds.nodes[0] + (size_t)k * (S + 1);
     {  // the same tree once, as sibling pairs (layouts.h, DScene::pairs) — when the six arrays ARE six pre-orders of one binary tree
         std::vector<NodeRec> tree;
         std::vector<PairRec> pairs;
         int depth = 0;
-        c->ds.pairs = nullptr;
-        c->ds.treeDepth = 0;
+        c->scene.ds.pairs = nullptr;
+        c->scene.ds.treeDepth = 0;
         // (a walker keeps a strip of treeDepth entries per lane in global memory for the deep end of its stack: a degenerate tree — a
         // chain thousands of levels deep — keeps the threaded walk, which needs no stack)
         constexpr int kMaxPairDepth = 2048;
         if (buildSharedTree(d, S, tree, pairs, depth) && depth <= kMaxPairDepth) {
-            if ((rc = uploadVec(c, pairs, &c->ds.pairs))) return rc;
-            c->ds.treeDepth = depth;
-            c->ds.rootLo = make_float4(tree[0].lo_prim.x, tree[0].lo_prim.y, tree[0].lo_prim.z,
+            if ((rc = uploadVec(c, pairs, &c->scene.ds.pairs))) return rc;
+            c->scene.ds.treeDepth = depth;
+            c->scene.ds.rootLo = make_float4(tree[0].lo_prim.x, tree[0].lo_prim.y, tree[0].lo_prim.z,
                                        asFloat(__builtin_bit_cast(int, tree[0].lo_prim.w) >= 0 ? __builtin_bit_cast(int, tree[0].lo_prim.w) : ~0));
-            c->ds.rootHi = tree[0].hi_next;
+            c->scene.ds.rootHi = tree[0].hi_next;
         }
     }
 
@@ -1163,22 +1209,19 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
         lights[i].b = make_float4(v[4], v[5], v[6], v[7]);
         lights[i].c = make_float4(v[8], r[0], r[1], r[2]);
     }
-    if ((rc = uploadVec(c, lights, &c->ds.lights))) return rc;
+    if ((rc = uploadVec(c, lights, &c->scene.ds.lights))) return rc;
     {  // kept for rdh_scene_update_geometry, which rebuilds the LightRecs from moved vertices
         std::vector<int> lp(d->lightPrimIds, d->lightPrimIds + d->numLights);
         const int *dp = nullptr;
         if ((rc = uploadVec(c, lp, &dp))) return rc;
-        c->dLightPrims = const_cast<int *>(dp);
-        c->numLights = d->numLights;
+        c->scene.dLightPrims = const_cast<int *>(dp);
+        c->scene.numLights = d->numLights;
     }
     {  // per-light constants of the RIS loop, computed on the device with the functions the per-candidate code uses
-        void *pre = nullptr;
-        HIP_TRY(c, hipMalloc(&pre, std::max<size_t>(sizeof(LightPre) * lights.size(), 64)));
-        c->sceneAllocs.push_back(pre);
-        c->ds.lightPre = static_cast<const LightPre *>(pre);
+        if ((rc = sceneAlloc(c, &c->scene.ds.lightPre, sizeof(LightPre) * lights.size()))) return rc;
         if (!lights.empty()) {
-            hipLaunchKernelGGL(k_light_precompute, dim3((unsigned)((lights.size() + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights,
-                               static_cast<LightPre *>(pre), (int)lights.size(), d->sumLightPowerInv);
+            hipLaunchKernelGGL(k_light_precompute, dim3((unsigned)((lights.size() + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.lights,
+                               const_cast<LightPre *>(c->scene.ds.lightPre), (int)lights.size(), d->sumLightPowerInv);
             HIP_TRY(c, hipStreamSynchronize(c->stream));
         }
     }
@@ -1186,24 +1229,23 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
     if (d->lightSamplerLength) memcpy(alias.data(), d->lightSampler, sizeof(AliasRec) * alias.size());
     for (auto &e : alias)
         if (e.failId < 0 || e.failId >= d->lightSamplerLength) return fail(c, RDH_ERR_ARGS, "alias table failId out of range");
-    if ((rc = uploadVec(c, alias, &c->ds.lightAlias))) return rc;
+    if ((rc = uploadVec(c, alias, &c->scene.ds.lightAlias))) return rc;
     std::vector<uint32_t> sobol(d->sampleSequence, d->sampleSequence + 10000 * 200);
-    if ((rc = uploadVec(c, sobol, &c->ds.sobol))) return rc;
+    if ((rc = uploadVec(c, sobol, &c->scene.ds.sobol))) return rc;
 
-    c->ds.counters = c->dCounters;
-    c->ds.bvhSize = S;
-    c->ds.numPrims = N;
-    c->ds.lightSamplerLength = d->lightSamplerLength;
-    c->ds.sumLightPowerInv = d->sumLightPowerInv;
-    c->lightCap = d->numLights;
-    c->lightLenCap = d->lightSamplerLength;
-    c->hostMats.assign(hm, hm + d->numMaterials);  // rdh_scene_set_materials edits these and counts emitters from them
-    c->matPrims.assign((size_t)d->numMaterials, 0);
-    for (int p = 0; p < N; p++) c->matPrims[(size_t)d->materialIds[p]]++;
-    c->matStamp.assign((size_t)d->numMaterials, 0u);
-    c->matEpoch = 0;
-    c->numTextures = d->numTextures;
-    c->haveScene = true;
+    c->scene.ds.counters = c->dCounters;
+    c->scene.ds.bvhSize = S;
+    c->scene.ds.numPrims = N;
+    c->scene.ds.lightSamplerLength = d->lightSamplerLength;
+    c->scene.ds.sumLightPowerInv = d->sumLightPowerInv;
+    c->scene.lightCap = d->numLights;
+    c->scene.lightLenCap = d->lightSamplerLength;
+    c->scene.hostMats.assign(hm, hm + d->numMaterials);  // rdh_scene_set_materials edits these and counts emitters from them
+    c->scene.matPrims.assign((size_t)d->numMaterials, 0);
+    for (int p = 0; p < N; p++) c->scene.matPrims[(size_t)d->materialIds[p]]++;
+    c->scene.edited.reset((size_t)d->numMaterials);
+    c->scene.numTextures = d->numTextures;
+    c->scene.haveScene = true;
     c->orderValid = false;
     return RDH_OK;
 }
@@ -1273,34 +1315,25 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
         withBools([&](auto pr) { rc = residentGrid(c, k_pt_persistent<false, pr.value>, 64, &resGrid); }, pairs);
         if (rc) return rc;
         const unsigned grid = sharedGrid(c, resGrid, groups);
-        const int ovfDepth = c->ds.treeDepth + 1;
+        const int ovfDepth = c->scene.ds.treeDepth + 1;
         if (pairs && (rc = ensureStackOverflow(c, resGrid))) return rc;
         // longest-paths-first schedule from the previous launch's per-block costs (same partition and resolution only)
         if (c->costBlocks != pm.numBlocks) {
             HIP_TRY(c, hipStreamSynchronize(c->sideStream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
-            for (int k = 0; k < 2; k++) {
-                if (c->blockCost[k]) hipFree(c->blockCost[k]);
-                if (c->blockOrder[k]) hipFree(c->blockOrder[k]);
-                c->blockCost[k] = nullptr;
-                c->blockOrder[k] = nullptr;
-            }
-            if (c->blockEma) hipFree(c->blockEma);
-            c->blockEma = nullptr;
             c->costBlocks = 0;
-            for (int k = 0; k < 2; k++) {
-                HIP_TRY(c, hipMalloc((void **)&c->blockCost[k], sizeof(unsigned) * (size_t)pm.numBlocks));
-                HIP_TRY(c, hipMalloc((void **)&c->blockOrder[k], sizeof(int) * (size_t)pm.numBlocks));
+            for (GrowBuf *b : {&c->blockCost[0], &c->blockCost[1], &c->blockOrder[0], &c->blockOrder[1], &c->blockEma}) {
+                b->release();  // sized for this frame, also when it has fewer blocks than the last (both streams are idle)
+                if ((rc = grow(c, *b, (size_t)pm.numBlocks, sizeof(unsigned) * (size_t)pm.numBlocks, Busy::Nothing))) return rc;
             }
-            HIP_TRY(c, hipMalloc((void **)&c->blockEma, sizeof(unsigned) * (size_t)pm.numBlocks));
-            HIP_TRY(c, hipMemsetAsync(c->blockEma, 0, sizeof(unsigned) * (size_t)pm.numBlocks, c->stream));
+            HIP_TRY(c, hipMemsetAsync(c->blockEma.p, 0, sizeof(unsigned) * (size_t)pm.numBlocks, c->stream));
             c->costBlocks = pm.numBlocks;
             c->orderValid = false;
         }
         if (!c->orderValid) {  // restart: no schedule in flight, both cost buffers zero, two launches in plain order
             HIP_TRY(c, hipStreamSynchronize(c->sideStream));
             for (int k = 0; k < 2; k++)
-                HIP_TRY(c, hipMemsetAsync(c->blockCost[k], 0, sizeof(unsigned) * (size_t)pm.numBlocks, c->stream));
+                HIP_TRY(c, hipMemsetAsync(c->blockCost[k].p, 0, sizeof(unsigned) * (size_t)pm.numBlocks, c->stream));
             c->persistFrame = 0;
             c->orderValid = true;
         }
@@ -1311,26 +1344,26 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
         if (n >= 2) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->evSched[cb], 0));
         const bool useOrder = n >= 2 && !(flags & RDH_PT_NO_SCHEDULE);
         HIP_TRY(c, hipMemsetAsync(c->dPersist, 0, offsetof(PersistCounters, deferred), c->stream));
-        const int *order = useOrder ? c->blockOrder[cb] : nullptr;
+        const int *order = useOrder ? c->blockOrder[cb].as<int>() : nullptr;
         long pp = profBegin(c, flags);
         int2 *const ovf = pairs ? c->treeOvf.as<int2>() : nullptr;
         withBools([&](auto cnt, auto pr) {
-            hipLaunchKernelGGL((k_pt_persistent<cnt.value, pr.value>), dim3(grid), dim3(64), 0, c->stream, c->ds, c->cam, pm, looper, iter,
-                               maxDepth, d_direct, d_indirect, c->dPersist, order, c->blockCost[cb], ovf, pairs ? ovfDepth : 0);
+            hipLaunchKernelGGL((k_pt_persistent<cnt.value, pr.value>), dim3(grid), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper, iter,
+                               maxDepth, d_direct, d_indirect, c->dPersist, order, c->blockCost[cb].as<unsigned>(), ovf, pairs ? ovfDepth : 0);
         }, count, pairs);
         profEnd(c, pp);
         // this launch's costs -> running means -> block order for launch n + 2, on the side stream
         HIP_TRY(c, hipEventRecord(c->evFrame, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->sideStream, c->evFrame, 0));
-        hipLaunchKernelGGL(k_persist_schedule, dim3(1), dim3(kScheduleThreads), 0, c->sideStream, c->blockCost[cb], c->blockEma,
-                           c->blockOrder[cb], pm.numBlocks);
+        hipLaunchKernelGGL(k_persist_schedule, dim3(1), dim3(kScheduleThreads), 0, c->sideStream, c->blockCost[cb].as<unsigned>(),
+                           c->blockEma.as<unsigned>(), c->blockOrder[cb].as<int>(), pm.numBlocks);
         HIP_TRY(c, hipEventRecord(c->evSched[cb], c->sideStream));
         return timeEnd(c, "pathTrace (persistent)");
     }
     timeBegin(c);
     long pe = profBegin(c, flags);
     withBools([&](auto cnt) {
-        hipLaunchKernelGGL(k_path_trace_mega<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->ds, c->cam, pm, looper,
+        hipLaunchKernelGGL(k_path_trace_mega<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper,
                            iter, maxDepth, d_direct, d_indirect);
     }, count);
     profEnd(c, pe);
@@ -1382,7 +1415,7 @@ int rdh_path_trace_direct(rdh_ctx *c, float *d_direct, int iter, int looper, uin
     PixelMap pm = makePixelMap(c);
     timeBegin(c);
     withBools([&](auto cnt) {
-        hipLaunchKernelGGL(k_path_trace_direct<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->ds, c->cam, pm, looper,
+        hipLaunchKernelGGL(k_path_trace_direct<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper,
                            iter, d_direct);
     }, (flags & RDH_PT_COUNT) != 0);
     return timeEnd(c, "pathTraceDirect");
@@ -1394,7 +1427,7 @@ int rdh_gbuffer_render(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
     int rc = requireReady(c);
     if (rc) return rc;
     if ((rc = enqueueGBuffer(c, gb, flags))) return rc;
-    c->movedSinceRender = false;  // rdh_scene_track_motion: "previous" is from now on what this render saw
+    c->scene.movedSinceRender = false;  // rdh_scene_track_motion: "previous" is from now on what this render saw
     return RDH_OK;
 }
 
@@ -1422,19 +1455,19 @@ static int enqueueGBuffer(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
     }
     DCamera last = toDeviceCamera(gb->lastCam);
     GBufPtrs p{gb->albedo, gb->normal[gb->frameIdx], gb->motion, gb->depth[gb->frameIdx], gb->primId[gb->frameIdx],
-               gb->width, gb->height, c->movedSinceRender ? c->prevTris : nullptr};
+               gb->width, gb->height, c->scene.movedSinceRender ? c->scene.prevTris : nullptr};
     const bool count = (flags & RDH_PT_COUNT) != 0;
     if (flags & RDH_PT_ONE_LANE_PER_PIXEL) {  // one lane per pixel for the whole launch (the reference's structure)
         timeBegin(c);
         withBools([&](auto cnt) {
-            hipLaunchKernelGGL(k_gbuffer<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->ds, c->cam, last, pm, p);
+            hipLaunchKernelGGL(k_gbuffer<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, last, pm, p);
         }, count);
         return timeEnd(c, "renderGBuffer");
     }
     // Primary rays are coherent: while the six threaded arrays sit in the caches the pair walk buys them nothing (teapots, 201 k nodes:
     // 0.78 ms either way, profiles/r03_o_*); it is taken where those arrays outgrow the 256-MiB Infinity Cache (6 x 32 B x nodes).
     static const int gbufPairsEnv = getenv("RADISH_GBUFFER_PAIRS") ? atoi(getenv("RADISH_GBUFFER_PAIRS")) : -1;  // experiments
-    const bool pairs = usePairs(c, flags) && (gbufPairsEnv >= 0 ? gbufPairsEnv != 0 : (size_t)c->ds.bvhSize * 192 > ((size_t)256 << 20));
+    const bool pairs = usePairs(c, flags) && (gbufPairsEnv >= 0 ? gbufPairsEnv != 0 : (size_t)c->scene.ds.bvhSize * 192 > ((size_t)256 << 20));
     // persistent launch with lane refill: as many single-wave workgroups as stay resident, never more than there is work.  This
     // pass does not divide by the context's share, and its strip is allocated also when the packet kernel runs (both kept as found).
     unsigned resGrid = 0;
@@ -1442,7 +1475,7 @@ static int enqueueGBuffer(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
     if (rc) return rc;
     const unsigned groups = (((unsigned)(pm.numBlocks + 3) / 4 + 7u) / 8u) * 8u * 4u;
     const unsigned grid = std::min(groups, resGrid);
-    const int ovfDepth = c->ds.treeDepth + 1;
+    const int ovfDepth = c->scene.ds.treeDepth + 1;
     if (pairs && (rc = ensureStackOverflow(c, resGrid))) return rc;
     int2 *const ovf = pairs ? c->treeOvf.as<int2>() : nullptr;
     timeBegin(c);
@@ -1453,21 +1486,21 @@ static int enqueueGBuffer(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
     const bool defer = !(flags & RDH_PT_NO_DEFER);
     if (defer) {
         const unsigned pixels = (unsigned)(c->cam.resx * c->cam.resy);
-        hipLaunchKernelGGL(k_gbuffer_find_literal, dim3((pixels + 255u) / 256u), dim3(256), 0, c->stream, c->ds, c->cam, pm, c->dPersist);
+        hipLaunchKernelGGL(k_gbuffer_find_literal, dim3((pixels + 255u) / 256u), dim3(256), 0, c->stream, c->scene.ds, c->cam, pm, c->dPersist);
         if ((rc = forkLiteral(c))) return rc;
         withBools([&](auto cnt) {
-            hipLaunchKernelGGL(k_gbuffer_literal<cnt.value>, dim3(kDeferCap), dim3(kWgTraceThreads), 0, c->litStream, c->ds, c->cam, last, p, c->dPersist);
+            hipLaunchKernelGGL(k_gbuffer_literal<cnt.value>, dim3(kDeferCap), dim3(kWgTraceThreads), 0, c->litStream, c->scene.ds, c->cam, last, p, c->dPersist);
         }, count);
     }
     if (usePackets(flags)) {  // one 8x8 block per wave, its 64 centre rays walked as a packet (kernels_persist.h, k_gbuffer_packet)
         const unsigned pgrid = ((unsigned)pm.numBlocks + 3u) / 4u;
         withBools([&](auto cnt, auto def) {
-            hipLaunchKernelGGL((k_gbuffer_packet<cnt.value, def.value>), dim3(pgrid), dim3(256), 0, c->stream, c->ds, c->cam, last, pm, p, c->dPersist,
+            hipLaunchKernelGGL((k_gbuffer_packet<cnt.value, def.value>), dim3(pgrid), dim3(256), 0, c->stream, c->scene.ds, c->cam, last, pm, p, c->dPersist,
                                packetBudget(flags));
         }, count, defer);
     } else {
         withBools([&](auto cnt, auto def, auto pr) {
-            hipLaunchKernelGGL((k_gbuffer_persistent<cnt.value, def.value, pr.value>), dim3(grid), dim3(64), 0, c->stream, c->ds, c->cam, last, pm, p,
+            hipLaunchKernelGGL((k_gbuffer_persistent<cnt.value, def.value, pr.value>), dim3(grid), dim3(64), 0, c->stream, c->scene.ds, c->cam, last, pm, p,
                                c->dPersist, ovf, pairs ? ovfDepth : 0);
         }, count, defer, pairs);
     }
@@ -1561,7 +1594,7 @@ int rdh_restir_direct(rdh_ctx *c, float *d_direct, int iter, int looper, const r
         const unsigned grid1 = ((nBlocks1 + 7u) / 8u) * 8u;
         if ((rc = waitExchanges(c, true, true))) return rc;  // pass 1 reads the G-buffer and last frame's reservoirs (temporal reuse)
         withBools([&](auto cnt) {
-            hipLaunchKernelGGL(k_restir_pass1<cnt.value>, dim3(grid1), dim3(p1Threads), 0, c->stream, c->ds, c->cam, pm, looper, iter, a, d_direct, apronBlocks);
+            hipLaunchKernelGGL(k_restir_pass1<cnt.value>, dim3(grid1), dim3(p1Threads), 0, c->stream, c->scene.ds, c->cam, pm, looper, iter, a, d_direct, apronBlocks);
         }, (flags & RDH_PT_COUNT) != 0);
     } else {
         // raygen -> closest-hit walk -> RIS (LDS light table) -> any-hit walk -> resolve (kernels_restir.h)
@@ -1573,20 +1606,20 @@ int rdh_restir_direct(rdh_ctx *c, float *d_direct, int iter, int looper, const r
         HIP_TRY(c, hipMemsetAsync(sp.deferCount, 0, 16, c->stream));
         const bool count = (flags & RDH_PT_COUNT) != 0;
         const unsigned gridBlk = (nBlocks1 + 3u) / 4u;
-        hipLaunchKernelGGL(k_restir_raygen, dim3(gridBlk), dim3(256), 0, c->stream, c->ds, c->cam, pm, looper, apronBlocks, sp.rays,
+        hipLaunchKernelGGL(k_restir_raygen, dim3(gridBlk), dim3(256), 0, c->stream, c->scene.ds, c->cam, pm, looper, apronBlocks, sp.rays,
                            sp.deferCount, sp.deferList);
         const bool pairs = usePairs(c, flags);
         if ((rc = launchWalk(c, sp.rays, slots, sp.hits, nullptr, count, defer ? sp.deferCount : nullptr, sp.deferList, 1, pairs, usePackets(flags),
                              packetBudget(flags)))) return rc;
-        const int nLights = c->ds.lightSamplerLength - (c->ds.envSamplerLength != 0 ? 1 : 0);
-        const size_t ldsBytes = (size_t)nLights * sizeof(LightPre) + (size_t)c->ds.lightSamplerLength * sizeof(AliasRec);
+        const int nLights = c->scene.ds.lightSamplerLength - (c->scene.ds.envSamplerLength != 0 ? 1 : 0);
+        const size_t ldsBytes = (size_t)nLights * sizeof(LightPre) + (size_t)c->scene.ds.lightSamplerLength * sizeof(AliasRec);
         const bool staged = nLights > 0 && ldsBytes <= kRisLdsBytes;
         int cus = 0;
         if ((rc = cuCount(c, &cus))) return rc;
         const unsigned wgNeeded = (nBlocks1 + (kRisThreads / 64) - 1) / (kRisThreads / 64);
         const unsigned risGrid = std::min(wgNeeded, (unsigned)(2 * cus));  // two 512-thread workgroups per CU (74 KB of LDS each at 1 026 lights)
         withBools([&](auto stg) {
-            hipLaunchKernelGGL(k_restir_ris<stg.value>, dim3(risGrid), dim3(kRisThreads), staged ? ldsBytes : 0, c->stream, c->ds, c->cam, pm, looper, a, apronBlocks, sp);
+            hipLaunchKernelGGL(k_restir_ris<stg.value>, dim3(risGrid), dim3(kRisThreads), staged ? ldsBytes : 0, c->stream, c->scene.ds, c->cam, pm, looper, a, apronBlocks, sp);
         }, staged);
         if ((rc = launchWalk(c, sp.segs, slots, nullptr, sp.occ, count, defer ? sp.deferCount + 1 : nullptr, sp.deferList + kRestirDeferCap, 1, pairs)))
             return rc;
@@ -1594,10 +1627,10 @@ int rdh_restir_direct(rdh_ctx *c, float *d_direct, int iter, int looper, const r
         // reuse in pass 2): exchanges of either that are still in flight on the communication stream have had the ray generation,
         // both walks and the RIS launch to hide behind.
         if ((rc = waitExchanges(c, true, true))) return rc;
-        hipLaunchKernelGGL(k_restir_resolve, dim3(gridBlk), dim3(256), 0, c->stream, c->ds, pm, iter, a, apronBlocks, sp, d_direct);
+        hipLaunchKernelGGL(k_restir_resolve, dim3(gridBlk), dim3(256), 0, c->stream, c->scene.ds, pm, iter, a, apronBlocks, sp, d_direct);
     }
     if (p->reuseMask & 2)
-        hipLaunchKernelGGL(k_restir_pass2, dim3(gridFor(pm)), dim3(256), 0, c->stream, c->ds, pm, iter, a, d_direct);
+        hipLaunchKernelGGL(k_restir_pass2, dim3(gridFor(pm)), dim3(256), 0, c->stream, c->scene.ds, pm, iter, a, d_direct);
     rc = timeEnd(c, "ReSTIR Direct");
     std::swap(c->resvCur, c->resvLast);  // restir.cu:221
     c->restirFirstFrame = false;         // :223-225
@@ -1733,10 +1766,8 @@ int commEnsure(rdh_ctx *c, GrowBuf &b, size_t floats) { return grow(c, b, floats
 int commStreamEnsure(rdh_ctx *c) {
     if (c->commStream) return RDH_OK;
     HIP_TRY(c, hipStreamCreateWithFlags(&c->commStream, hipStreamNonBlocking));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->evToComm, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->evGbuf, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->evImg, hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&c->evResv, hipEventDisableTiming));
+    for (hipEvent_t *e : {&c->evToComm, &c->evGbuf, &c->evImg, &c->evResv})
+        if (int rc = newEvent(c, e)) return rc;
     return RDH_OK;
 }
 bool overlapOn(const rdh_ctx *c) { return c->commOverlap && c->commStream != nullptr; }
@@ -2195,7 +2226,7 @@ static int walkPersistent(rdh_ctx *c, const float *d_rays, int64_t n, int4 *d_hi
         const unsigned g = (unsigned)(n < 4096 ? n : 4096);
         timeBegin(c);
         withBools([&](auto cnt, auto any) {
-            hipLaunchKernelGGL((k_trace_wg<cnt.value, any.value>), dim3(g), dim3(kWgTraceThreads), 0, c->stream, c->ds, d_rays, (long long)n, d_hits, d_occ);
+            hipLaunchKernelGGL((k_trace_wg<cnt.value, any.value>), dim3(g), dim3(kWgTraceThreads), 0, c->stream, c->scene.ds, d_rays, (long long)n, d_hits, d_occ);
         }, (flags & RDH_PT_COUNT) != 0, d_occ != nullptr);
         return timeEnd(c, what);
     }
@@ -2208,7 +2239,7 @@ static int walkPersistent(rdh_ctx *c, const float *d_rays, int64_t n, int4 *d_hi
 
 int rdh_trace_closest(rdh_ctx *c, const float *d_rays, int64_t n, rdh_hit *d_hits, uint32_t flags) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
     if (int rc = settleTree(c)) return rc;
     if (n < 0 || (n > 0 && (!d_rays || !d_hits))) return fail(c, RDH_ERR_ARGS, "rdh_trace_closest: bad arguments");
     if (n == 0) return RDH_OK;
@@ -2217,14 +2248,14 @@ int rdh_trace_closest(rdh_ctx *c, const float *d_rays, int64_t n, rdh_hit *d_hit
     unsigned grid = (unsigned)((n + 255) / 256);
     timeBegin(c);
     withBools([&](auto cnt) {
-        hipLaunchKernelGGL(k_trace_closest<cnt.value>, dim3(grid), dim3(256), 0, c->stream, c->ds, d_rays, (long long)n, (int4 *)d_hits);
+        hipLaunchKernelGGL(k_trace_closest<cnt.value>, dim3(grid), dim3(256), 0, c->stream, c->scene.ds, d_rays, (long long)n, (int4 *)d_hits);
     }, (flags & RDH_PT_COUNT) != 0);
     return timeEnd(c, "trace_closest");
 }
 
 int rdh_trace_occluded(rdh_ctx *c, const float *d_seg, int64_t n, int32_t *d_occ, uint32_t flags) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
     if (int rc = settleTree(c)) return rc;
     if (n < 0 || (n > 0 && (!d_seg || !d_occ))) return fail(c, RDH_ERR_ARGS, "rdh_trace_occluded: bad arguments");
     if (n == 0) return RDH_OK;
@@ -2233,7 +2264,7 @@ int rdh_trace_occluded(rdh_ctx *c, const float *d_seg, int64_t n, int32_t *d_occ
     unsigned grid = (unsigned)((n + 255) / 256);
     timeBegin(c);
     withBools([&](auto cnt) {
-        hipLaunchKernelGGL(k_trace_occluded<cnt.value>, dim3(grid), dim3(256), 0, c->stream, c->ds, d_seg, (long long)n, d_occ);
+        hipLaunchKernelGGL(k_trace_occluded<cnt.value>, dim3(grid), dim3(256), 0, c->stream, c->scene.ds, d_seg, (long long)n, d_occ);
     }, (flags & RDH_PT_COUNT) != 0);
     return timeEnd(c, "trace_occluded");
 }
@@ -2259,7 +2290,7 @@ int rdh_dump_rays(rdh_ctx *c, int looper, int maxDepth, float *d_closest, int64_
     hipMemsetAsync(cnt, 0, 16, c->stream);
     hipMemsetAsync(img, 0, px * 6 * sizeof(float), c->stream);
     RayDump d{d_closest, d_any, (long long)capClosest, (long long)capAny, cnt};
-    hipLaunchKernelGGL((k_path_trace_mega<false, true>), dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->ds, c->cam, pm, looper, 0,
+    hipLaunchKernelGGL((k_path_trace_mega<false, true>), dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper, 0,
                        maxDepth, img, img + px * 3, d);
     unsigned long long h[2] = {0, 0};
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -2586,12 +2617,12 @@ size_t aliasWorkBytes(int n) {
 
 // Shared by rdh_scene_update_geometry and rdh_scene_refit_geometry.
 int checkGeomArgs(rdh_ctx *c, const char *what, const float *d_vertices, const rdh_light_update *lights) {
-    if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "%s: no scene uploaded", what);
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_ARGS, "%s: no scene uploaded", what);  // (not RDH_ERR_NO_SCENE: kept as found)
     if (!d_vertices) return fail(c, RDH_ERR_ARGS, "%s: d_vertices is null", what);
     if (lights) {
-        if (lights->lightSamplerLength != c->ds.lightSamplerLength)
+        if (lights->lightSamplerLength != c->scene.ds.lightSamplerLength)
             return fail(c, RDH_ERR_ARGS, "%s: lightSamplerLength %d != the scene's %d", what, lights->lightSamplerLength,
-                        c->ds.lightSamplerLength);
+                        c->scene.ds.lightSamplerLength);
         if (lights->lightSamplerLength > 0 && !lights->lightSampler) return fail(c, RDH_ERR_ARGS, "%s: lightSampler is null", what);
         const AliasRec *a = static_cast<const AliasRec *>(lights->lightSampler);
         for (int i = 0; i < lights->lightSamplerLength; i++)
@@ -2602,13 +2633,20 @@ int checkGeomArgs(rdh_ctx *c, const char *what, const float *d_vertices, const r
 }
 
 int ensureTreeHeader(rdh_ctx *c) {
-    if (!c->evTree) {
-        HIP_TRY(c, hipEventCreateWithFlags(&c->evTree, hipEventDisableTiming));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->evUpdWait, hipEventDisableTiming));
-        for (int k = 0; k < 2; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->evAliasStage[k], hipEventDisableTiming));
-        HIP_TRY(c, hipMalloc((void **)&c->dTreeHdr, 3 * sizeof(int4)));
-        HIP_TRY(c, hipHostMalloc((void **)&c->hTreeHdr, 3 * sizeof(int4), hipHostMallocDefault));
-    }
+    if (c->evUpdWait) return RDH_OK;
+    int rc;
+    if ((rc = grow(c, c->dTreeHdr, 3, 3 * sizeof(int4), Busy::Nothing)) || (rc = grow(c, c->hTreeHdr, 3, 3 * sizeof(int4), Busy::Nothing))) return rc;
+    if (!c->evTree && (rc = newEvent(c, &c->evTree))) return rc;
+    return newEvent(c, &c->evUpdWait);
+}
+
+// The copy of a tree header into hTreeHdr has just been enqueued: settleTree folds it into ds before the next launch.  `refit`: the
+// header is a refit's, of which only the root box counts.
+int treeHeaderPending(rdh_ctx *c, bool refit) {
+    HIP_TRY(c, hipEventRecord(c->evTree, c->stream));
+    c->scene.treePending = true;
+    c->scene.treeRefit = refit;
+    c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
     return RDH_OK;
 }
 
@@ -2624,40 +2662,39 @@ int waitSideStreams(rdh_ctx *c) {
 
 // Triangles, attributes, emissive triangles, the light table and the per-light constants, on the context's stream.
 int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
-    const int N = c->ds.numPrims;
-    const int geomN = std::max(N, c->numLights);
-    c->worldStale = true;  // rdh_scene_pose_objects clears this again when the arrays were its own
+    const int N = c->scene.ds.numPrims;
+    const int geomN = std::max(N, c->scene.numLights);
+    c->scene.worldStale = true;  // rdh_scene_pose_objects clears this again when the arrays were its own
     // rdh_scene_track_motion: the first update since the last G-buffer render keeps what that render saw; a later one must not
     TriRec *keep = nullptr;
-    if (c->prevTris && !c->movedSinceRender) {
-        keep = c->prevTris;
-        c->movedSinceRender = true;
+    if (c->scene.prevTris && !c->scene.movedSinceRender) {
+        keep = c->scene.prevTris;
+        c->scene.movedSinceRender = true;
     }
     hipLaunchKernelGGL(k_geom_update, dim3((unsigned)((geomN + 255) / 256)), dim3(256), 0, c->stream, d_vertices, d_normals,
-                       const_cast<TriRec *>(c->ds.tris), const_cast<AttrRec *>(c->ds.attrs), N, const_cast<LightRec *>(c->ds.lights),
-                       (const int *)c->dLightPrims, c->numLights, keep);
+                       const_cast<TriRec *>(c->scene.ds.tris), const_cast<AttrRec *>(c->scene.ds.attrs), N, const_cast<LightRec *>(c->scene.ds.lights),
+                       (const int *)c->scene.dLightPrims, c->scene.numLights, keep);
     if (lights && lights->lightSamplerLength > 0) {  // the caller's table goes through a pinned staging buffer: no host wait
-        const int s = c->aliasStageNext, len = lights->lightSamplerLength;
-        c->aliasStageNext ^= 1;
-        HIP_TRY(c, hipEventSynchronize(c->evAliasStage[s]));  // the copy of two updates ago (long done, normally)
-        if (int rc = grow(c, c->hAliasStage[s], (size_t)len, sizeof(AliasRec) * len, Busy::Nothing)) return rc;  // (the event above: its last copy is done)
-        memcpy(c->hAliasStage[s].p, lights->lightSampler, sizeof(AliasRec) * len);
-        HIP_TRY(c, hipMemcpyAsync(const_cast<AliasRec *>(c->ds.lightAlias), c->hAliasStage[s].p, sizeof(AliasRec) * len, hipMemcpyHostToDevice,
-                                  c->stream));
-        HIP_TRY(c, hipEventRecord(c->evAliasStage[s], c->stream));
+        // (this site used to turn to the other buffer before the wait instead of after the copy: which buffer a call that failed in
+        // between left to the next call is not observable)
+        const size_t bytes = sizeof(AliasRec) * (size_t)lights->lightSamplerLength;
+        AliasRec *host = nullptr;
+        if (int rc = stageTake(c, c->aliasStage, (size_t)lights->lightSamplerLength, bytes, &host)) return rc;
+        memcpy(host, lights->lightSampler, bytes);
+        if (int rc = stageSend(c, c->aliasStage, const_cast<AliasRec *>(c->scene.ds.lightAlias), bytes)) return rc;
     }
     if (lights) {
-        c->ds.sumLightPowerInv = lights->sumLightPowerInv;
-        c->lightsPending = false;  // the caller's table and value replace those of a rebuild enqueued before this update
+        c->scene.ds.sumLightPowerInv = lights->sumLightPowerInv;
+        c->scene.lightsPending = false;  // the caller's table and value replace those of a rebuild enqueued before this update
     }
-    if (c->numLights > 0) {
-        const dim3 grid((unsigned)((c->numLights + 255) / 256));
-        if (c->lightsPending)  // a rebuild's value, not on the host yet: read it where the rebuild left it
-            hipLaunchKernelGGL(k_light_precompute_dev, grid, dim3(256), 0, c->stream, c->ds.lights, const_cast<LightPre *>(c->ds.lightPre),
-                               c->numLights, (const float *)lightWork(c->lightScratch, c->lightLenCap).sums + 1);
+    if (c->scene.numLights > 0) {
+        const dim3 grid((unsigned)((c->scene.numLights + 255) / 256));
+        if (c->scene.lightsPending)  // a rebuild's value, not on the host yet: read it where the rebuild left it
+            hipLaunchKernelGGL(k_light_precompute_dev, grid, dim3(256), 0, c->stream, c->scene.ds.lights, const_cast<LightPre *>(c->scene.ds.lightPre),
+                               c->scene.numLights, (const float *)lightWork(c->scene.lightScratch, c->scene.lightLenCap).sums + 1);
         else
-            hipLaunchKernelGGL(k_light_precompute, grid, dim3(256), 0, c->stream, c->ds.lights, const_cast<LightPre *>(c->ds.lightPre),
-                               c->numLights, c->ds.sumLightPowerInv);
+            hipLaunchKernelGGL(k_light_precompute, grid, dim3(256), 0, c->stream, c->scene.ds.lights, const_cast<LightPre *>(c->scene.ds.lightPre),
+                               c->scene.numLights, c->scene.ds.sumLightPowerInv);
     }
     return RDH_OK;
 }
@@ -2669,17 +2706,14 @@ int updateGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, 
     int rc = checkGeomArgs(c, what, d_vertices, lights);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    const int N = c->scene.ds.numPrims, S = c->scene.ds.bvhSize;
     if ((rc = ensureTreeHeader(c))) return rc;
     if ((rc = waitSideStreams(c))) return rc;
-    c->planValid = false;  // a new topology: the next refit derives its plan again
-    if (!c->ds.pairs && !c->updPairs) {  // the upload had no pairs; an updated tree always has them
-        void *p = nullptr;
-        HIP_TRY(c, hipMalloc(&p, sizeof(PairRec) * ((size_t)(S - 1) / 2 + 1)));
-        c->sceneAllocs.push_back(p);
-        c->updPairs = static_cast<PairRec *>(p);
+    c->scene.planValid = false;  // a new topology: the next refit derives its plan again
+    if (!c->scene.ds.pairs && !c->scene.updPairs) {  // the upload had no pairs; an updated tree always has them
+        if ((rc = sceneAlloc(c, &c->scene.updPairs, sizeof(PairRec) * ((size_t)(S - 1) / 2 + 1)))) return rc;
     }
-    PairRec *pairs = c->updPairs ? c->updPairs : const_cast<PairRec *>(c->ds.pairs);
+    PairRec *pairs = c->scene.updPairs ? c->scene.updPairs : const_cast<PairRec *>(c->scene.ds.pairs);
     BvhWork w{};
     LbvhWork L{};
     if ((rc = builder == RDH_BVH_LBVH ? lbvhWorkspace(c, N, L, w) : bvhWorkspace(c, N, w))) return rc;
@@ -2697,15 +2731,30 @@ int updateGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, 
     if ((rc = builder == RDH_BVH_LBVH ? launchLbvhBuild(c, L, w) : launchBvhBuild(c, w))) return rc;
     const long long recs = 6ll * (S + 1);
     hipLaunchKernelGGL(k_bvh_noderecs, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, c->stream, (const float *)w.boxes, w,
-                       const_cast<NodeRec *>(c->ds.nodes[0]), S);
-    hipLaunchKernelGGL(k_bvh_pairs, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, w, pairs, c->dTreeHdr);
+                       const_cast<NodeRec *>(c->scene.ds.nodes[0]), S);
+    hipLaunchKernelGGL(k_bvh_pairs, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, w, pairs, c->dTreeHdr.as<int4>());
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr, c->dTreeHdr, 3 * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipEventRecord(c->evTree, c->stream));
-    c->treePending = true;
-    c->treeRefit = false;  // this header is an update's (a refit's header still pending is superseded): settle all of it
-    c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
-    return RDH_OK;
+    HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr.p, c->dTreeHdr.p, 3 * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
+    return treeHeaderPending(c, false);  // an update's header (a refit's still pending is superseded): settle all of it
+}
+
+// rdh_build_bvh_device(_ex): the tree of a caller's soup into the caller's arrays, by `builder` (checked by the caller); `what` is
+// the entry that was called.
+int buildBvhDevice(rdh_ctx *c, const char *what, const float *d_vertices, int32_t numPrims, int builder, float *d_boxes,
+                   int32_t *const d_nodes[6]) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "%s: bad arguments", what);
+    for (int k = 0; k < 6; k++)
+        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "%s: d_nodes[%d] is null", what, k);
+    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "%s: %d primitives", what, numPrims);
+    HIP_TRY(c, hipSetDevice(c->device));
+    LbvhWork L{};
+    BvhWork w{};
+    if (int rc = builder == RDH_BVH_LBVH ? lbvhWorkspace(c, numPrims, L, w) : bvhWorkspace(c, numPrims, w)) return rc;
+    L.verts = w.verts = d_vertices;
+    w.boxes = d_boxes;
+    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
+    return builder == RDH_BVH_LBVH ? launchLbvhBuild(c, L, w) : launchBvhBuild(c, w);
 }
 
 }  // namespace
@@ -2713,39 +2762,16 @@ int updateGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, 
 extern "C" {
 
 int rdh_build_bvh_device(rdh_ctx *c, const float *d_vertices, int32_t numPrims, float *d_boxes, int32_t *const d_nodes[6]) {
-    if (!c) return RDH_ERR_ARGS;
-    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: bad arguments");
-    for (int k = 0; k < 6; k++)
-        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: d_nodes[%d] is null", k);
-    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device: %d primitives", numPrims);
-    HIP_TRY(c, hipSetDevice(c->device));
-    BvhWork w{};
-    int rc = bvhWorkspace(c, numPrims, w);
-    if (rc) return rc;
-    w.verts = d_vertices;
-    w.boxes = d_boxes;
-    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
-    return launchBvhBuild(c, w);
+    return buildBvhDevice(c, "rdh_build_bvh_device", d_vertices, numPrims, RDH_BVH_SAH, d_boxes, d_nodes);
 }
 
 int rdh_build_bvh_device_ex(rdh_ctx *c, const float *d_vertices, int32_t numPrims, int builder, float *d_boxes,
                             int32_t *const d_nodes[6]) {
     if (!c) return RDH_ERR_ARGS;
+    // (the SAH builder's messages name the entry without _ex: kept as found)
     if (builder == RDH_BVH_SAH) return rdh_build_bvh_device(c, d_vertices, numPrims, d_boxes, d_nodes);
     if (builder != RDH_BVH_LBVH) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: unknown builder %d", builder);
-    if (!d_vertices || numPrims <= 0 || !d_boxes || !d_nodes) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: bad arguments");
-    for (int k = 0; k < 6; k++)
-        if (!d_nodes[k]) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: d_nodes[%d] is null", k);
-    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_build_bvh_device_ex: %d primitives", numPrims);
-    HIP_TRY(c, hipSetDevice(c->device));
-    LbvhWork L{};
-    BvhWork w{};
-    int rc = lbvhWorkspace(c, numPrims, L, w);
-    if (rc) return rc;
-    L.verts = w.verts = d_vertices;
-    w.boxes = d_boxes;
-    for (int k = 0; k < 6; k++) w.nodes[k] = d_nodes[k];
-    return launchLbvhBuild(c, L, w);
+    return buildBvhDevice(c, "rdh_build_bvh_device_ex", d_vertices, numPrims, builder, d_boxes, d_nodes);
 }
 
 int rdh_scene_update_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights) {
@@ -2778,7 +2804,7 @@ struct RefitWork {  // carved from rdh_ctx::refitBuf; the arrival counters come 
 };
 
 int refitWork(rdh_ctx *c, RefitWork &r) {
-    const int N = c->ds.numPrims;
+    const int N = c->scene.ds.numPrims;
     const size_t S = 2 * (size_t)N - 1, blocks = (S + 255) / 256;
     return growCarved(c, c->refitBuf, (size_t)N, Busy::Stream, [&](Carver &k) {
         r.counters = k.take<int>(4 * S);
@@ -2794,8 +2820,8 @@ int refitWork(rdh_ctx *c, RefitWork &r) {
 }
 
 int launchTreeCost(rdh_ctx *c, const RefitWork &r, int slot) {
-    hipLaunchKernelGGL(k_tree_cost_partial, dim3(kCostBlocks), dim3(256), 0, c->stream, c->ds.nodes[0], c->ds.bvhSize, r.partial);
-    hipLaunchKernelGGL(k_tree_cost_final, dim3(1), dim3(256), 0, c->stream, c->ds.nodes[0], (const double *)r.partial, c->ds.bvhSize,
+    hipLaunchKernelGGL(k_tree_cost_partial, dim3(kCostBlocks), dim3(256), 0, c->stream, c->scene.ds.nodes[0], c->scene.ds.bvhSize, r.partial);
+    hipLaunchKernelGGL(k_tree_cost_final, dim3(1), dim3(256), 0, c->stream, c->scene.ds.nodes[0], (const double *)r.partial, c->scene.ds.bvhSize,
                        r.cost + slot);
     HIP_TRY(c, hipGetLastError());
     return RDH_OK;
@@ -2804,22 +2830,22 @@ int launchTreeCost(rdh_ctx *c, const RefitWork &r, int slot) {
 // The refit plan of the uploaded topology, derived from the six NodeRec arrays on the device, and the tree's cost as it stands
 // (sahAtBuild).  Blocking: the caller learns here whether the arrays are one tree.
 int buildRefitPlan(rdh_ctx *c, RefitWork &r) {
-    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    const int N = c->scene.ds.numPrims, S = c->scene.ds.bvhSize;
     const unsigned grid = (unsigned)((S + 255) / 256);
     HIP_TRY(c, hipMemsetAsync(r.counters, 0, 4 * (size_t)S, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.plan, 0xff, sizeof(RefitPlanRec) * (size_t)S, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.parentCount, 0, 4 * (size_t)S, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.primPos, 0xff, 4 * 6 * (size_t)N, c->stream));
     HIP_TRY(c, hipMemsetAsync(r.err, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_refit_links, dim3((unsigned)((6ll * S + 255) / 256)), dim3(256), 0, c->stream, c->ds.nodes[0], S, N, r.plan,
+    hipLaunchKernelGGL(k_refit_links, dim3((unsigned)((6ll * S + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.nodes[0], S, N, r.plan,
                        r.parentCount, r.primPos, r.err);
-    hipLaunchKernelGGL(k_refit_count, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, r.blockSums);
+    hipLaunchKernelGGL(k_refit_count, dim3(grid), dim3(256), 0, c->stream, c->scene.ds.nodes[0], S, r.blockSums);
     hipLaunchKernelGGL(k_refit_scan, dim3(1), dim3(256), 0, c->stream, r.blockSums, (int)grid);
-    hipLaunchKernelGGL(k_refit_number, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, (const int *)r.blockSums, r.plan);
-    hipLaunchKernelGGL(k_refit_plan_climb, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, N, r.plan, (const int *)r.primPos,
+    hipLaunchKernelGGL(k_refit_number, dim3(grid), dim3(256), 0, c->stream, c->scene.ds.nodes[0], S, (const int *)r.blockSums, r.plan);
+    hipLaunchKernelGGL(k_refit_plan_climb, dim3(grid), dim3(256), 0, c->stream, c->scene.ds.nodes[0], S, N, r.plan, (const int *)r.primPos,
                        r.counters, r.err);
-    hipLaunchKernelGGL(k_refit_check, dim3(grid), dim3(256), 0, c->stream, c->ds.nodes[0], S, (const RefitPlanRec *)r.plan,
-                       (const int *)r.parentCount, c->ds.pairs, r.err);
+    hipLaunchKernelGGL(k_refit_check, dim3(grid), dim3(256), 0, c->stream, c->scene.ds.nodes[0], S, (const RefitPlanRec *)r.plan,
+                       (const int *)r.parentCount, c->scene.ds.pairs, r.err);
     HIP_TRY(c, hipGetLastError());
     int rc = launchTreeCost(c, r, 1);
     if (rc) return rc;
@@ -2830,7 +2856,7 @@ int buildRefitPlan(rdh_ctx *c, RefitWork &r) {
         return fail(c, RDH_ERR_STATE,
                     "rdh_scene_refit_geometry: the scene's six node arrays are not six orderings of one tree with one primitive per "
                     "leaf (check bits %d); upload the scene again or call rdh_scene_update_geometry", err);
-    c->planValid = true;
+    c->scene.planValid = true;
     return RDH_OK;
 }
 
@@ -2845,53 +2871,43 @@ int rdh_scene_refit_geometry(rdh_ctx *c, const float *d_vertices, const float *d
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensureTreeHeader(c))) return rc;
     RefitWork r{};
-    if (!c->planValid) {
+    if (!c->scene.planValid) {
         if ((rc = settleTree(c))) return rc;  // the plan reads the update's tree; its header must be folded in first
         if ((rc = refitWork(c, r))) return rc;
         if ((rc = buildRefitPlan(c, r))) return rc;  // nothing has changed yet when this refuses
     } else if ((rc = refitWork(c, r))) {
         return rc;
     }
-    const int N = c->ds.numPrims, S = c->ds.bvhSize;
+    const int N = c->scene.ds.numPrims, S = c->scene.ds.bvhSize;
     if ((rc = waitSideStreams(c))) return rc;
     if ((rc = rewriteGeometry(c, d_vertices, d_normals, lights))) return rc;
     HIP_TRY(c, hipMemsetAsync(r.counters, 0, 4 * (size_t)std::max(N - 1, 1), c->stream));
     hipLaunchKernelGGL(k_refit, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, c->stream, d_vertices, (const RefitPlanRec *)r.plan,
-                       const_cast<NodeRec *>(c->ds.nodes[0]), const_cast<PairRec *>(c->ds.pairs), r.counters, r.rootBox, S);
+                       const_cast<NodeRec *>(c->scene.ds.nodes[0]), const_cast<PairRec *>(c->scene.ds.pairs), r.counters, r.rootBox, S);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr + 1, r.rootBox, 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipEventRecord(c->evTree, c->stream));
-    c->treePending = true;
-    c->treeRefit = true;
-    c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
-    return RDH_OK;
+    HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr.as<int4>() + 1, r.rootBox, 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    return treeHeaderPending(c, true);
 }
 
 int rdh_scene_track_motion(rdh_ctx *c, int enable) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_track_motion: no scene uploaded");
-    if ((enable != 0) == (c->prevTris != nullptr)) return RDH_OK;
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_track_motion: no scene uploaded");
+    if ((enable != 0) == (c->scene.prevTris != nullptr)) return RDH_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (enable) {  // "previous == current": nothing to copy, the first update after this fills the buffer before any kernel reads it
-        void *p = nullptr;
-        HIP_TRY(c, hipMalloc(&p, sizeof(TriRec) * (size_t)c->ds.numPrims));
-        c->sceneAllocs.push_back(p);
-        c->prevTris = static_cast<TriRec *>(p);
+        if (int rc = sceneAlloc(c, &c->scene.prevTris, sizeof(TriRec) * (size_t)c->scene.ds.numPrims)) return rc;
     } else {
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // a G-buffer render may still read the buffer (switching off is not a per-frame call)
-        void *p = c->prevTris;
-        c->sceneAllocs.erase(std::find(c->sceneAllocs.begin(), c->sceneAllocs.end(), p));
-        HIP_TRY(c, hipFree(p));
-        c->prevTris = nullptr;
+        if (int rc = sceneRelease(c, &c->scene.prevTris)) return rc;
     }
-    c->movedSinceRender = false;
+    c->scene.movedSinceRender = false;
     return RDH_OK;
 }
 
 int rdh_scene_tree_cost(rdh_ctx *c, double *sahNow, double *sahAtBuild) {
     if (!c) return RDH_ERR_ARGS;
     if (!sahNow || !sahAtBuild) return fail(c, RDH_ERR_ARGS, "rdh_scene_tree_cost: null output");
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_tree_cost: no scene uploaded");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_tree_cost: no scene uploaded");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = settleTree(c);
     if (rc) return rc;
@@ -2902,31 +2918,31 @@ int rdh_scene_tree_cost(rdh_ctx *c, double *sahNow, double *sahAtBuild) {
     HIP_TRY(c, hipMemcpyAsync(cost, r.cost, sizeof(cost), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *sahNow = cost[0];
-    *sahAtBuild = c->planValid ? cost[1] : cost[0];
+    *sahAtBuild = c->scene.planValid ? cost[1] : cost[0];
     return RDH_OK;
 }
 
 long long rdh_debug_read_tree(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
     if (int rc = settleTree(c)) return rc;
-    const int S = c->ds.bvhSize;
+    const int S = c->scene.ds.bvhSize;
     long long bytes;
     if (which == 0) bytes = (long long)sizeof(NodeRec) * 6 * (S + 1);
-    else if (which == 1) bytes = c->ds.pairs ? (long long)sizeof(PairRec) * ((S - 1) / 2 + 1) : 0;
+    else if (which == 1) bytes = c->scene.ds.pairs ? (long long)sizeof(PairRec) * ((S - 1) / 2 + 1) : 0;
     else if (which == 2) bytes = 48;
     else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_tree: which = %d", which);
     if (!hostOut) return bytes;
     if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_tree: %lld bytes needed", bytes);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (which == 0) HIP_TRY(c, hipMemcpy(hostOut, c->ds.nodes[0], bytes, hipMemcpyDeviceToHost));
-    else if (which == 1 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.pairs, bytes, hipMemcpyDeviceToHost));
+    if (which == 0) HIP_TRY(c, hipMemcpy(hostOut, c->scene.ds.nodes[0], bytes, hipMemcpyDeviceToHost));
+    else if (which == 1 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->scene.ds.pairs, bytes, hipMemcpyDeviceToHost));
     else if (which == 2) {
-        int32_t h[4] = {c->ds.treeDepth, c->ds.pairs ? 1 : 0, 0, 0};
+        int32_t h[4] = {c->scene.ds.treeDepth, c->scene.ds.pairs ? 1 : 0, 0, 0};
         memcpy(hostOut, h, 16);
-        memcpy(static_cast<char *>(hostOut) + 16, &c->ds.rootLo, 16);
-        memcpy(static_cast<char *>(hostOut) + 32, &c->ds.rootHi, 16);
+        memcpy(static_cast<char *>(hostOut) + 16, &c->scene.ds.rootLo, 16);
+        memcpy(static_cast<char *>(hostOut) + 32, &c->scene.ds.rootHi, 16);
     }
     return bytes;
 }
@@ -2949,7 +2965,7 @@ int growEmitWork(rdh_ctx *c, int numPrims, EmitWork *out) {
     const size_t blocks = ((size_t)numPrims + 255) / 256;
     const void *before = c->emitScratch.p;
     if (int rc = grow(c, c->emitScratch, std::max<size_t>(blocks, 1), sizeof(int) * (std::max<size_t>(blocks, 1) + 2), Busy::Stream)) return rc;
-    if (c->emitScratch.p != before) c->listEdited = false;  // the last edit's total went with the old buffer
+    if (c->emitScratch.p != before) c->scene.listEdited = false;  // the last edit's total went with the old buffer
     *out = emitWork(c->emitScratch);
     return RDH_OK;
 }
@@ -2980,67 +2996,58 @@ int rdh_build_alias_table_device(rdh_ctx *c, const float *d_values, int32_t n, v
 
 int rdh_scene_rebuild_lights(rdh_ctx *c, float envPower) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_ARGS, "rdh_scene_rebuild_lights: no scene uploaded");
-    const bool hasEnv = c->ds.envTex >= 0;
-    if (hasEnv && !(envPower >= 0.f && envPower <= FLT_MAX))
-        return fail(c, RDH_ERR_ARGS, "rdh_scene_rebuild_lights: envPower %g must be finite and not negative", (double)envPower);
-    const int len = c->ds.lightSamplerLength;
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_ARGS, "rdh_scene_rebuild_lights: no scene uploaded");
+    int rc = checkEnvPower(c, "rdh_scene_rebuild_lights", envPower);
+    if (rc) return rc;
+    const int len = c->scene.ds.lightSamplerLength;
     if (len == 0) return RDH_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensureTreeHeader(c);
-    if (rc) return rc;
-    if (!c->evLights) {
-        HIP_TRY(c, hipHostMalloc((void **)&c->hLightSums, 2 * sizeof(float), hipHostMallocDefault));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->evLights, hipEventDisableTiming));
-    }
-    if (!c->lightScratch) {
-        void *p = nullptr;
-        HIP_TRY(c, hipMalloc(&p, aliasWorkBytes(c->lightLenCap)));
-        c->sceneAllocs.push_back(p);
-        c->lightScratch = p;
-    }
+    if ((rc = ensureTreeHeader(c))) return rc;
+    if ((rc = grow(c, c->hLightSums, 2, 2 * sizeof(float), Busy::Nothing))) return rc;
+    if (!c->evLights && (rc = newEvent(c, &c->evLights))) return rc;
+    if (!c->scene.lightScratch && (rc = sceneAlloc(c, &c->scene.lightScratch, aliasWorkBytes(c->scene.lightLenCap)))) return rc;
     if ((rc = waitSideStreams(c))) return rc;  // the table and the per-light constants are rewritten in place
-    float *power = static_cast<float *>(c->lightScratch);
-    const AliasWork w = lightWork(c->lightScratch, c->lightLenCap);  // laid out for the capacity (rdh_scene_set_materials changes len)
-    hipLaunchKernelGGL(k_light_power, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights, c->numLights, len,
+    float *power = static_cast<float *>(c->scene.lightScratch);
+    const AliasWork w = lightWork(c->scene.lightScratch, c->scene.lightLenCap);  // laid out for the capacity (rdh_scene_set_materials changes len)
+    hipLaunchKernelGGL(k_light_power, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.lights, c->scene.numLights, len,
                        envPower, power);
-    launchAliasBuild(c, power, len, w, const_cast<AliasRec *>(c->ds.lightAlias));
-    if (c->numLights > 0)
-        hipLaunchKernelGGL(k_light_precompute_dev, dim3((unsigned)((c->numLights + 255) / 256)), dim3(256), 0, c->stream, c->ds.lights,
-                           const_cast<LightPre *>(c->ds.lightPre), c->numLights, (const float *)w.sums + 1);
+    launchAliasBuild(c, power, len, w, const_cast<AliasRec *>(c->scene.ds.lightAlias));
+    if (c->scene.numLights > 0)
+        hipLaunchKernelGGL(k_light_precompute_dev, dim3((unsigned)((c->scene.numLights + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.lights,
+                           const_cast<LightPre *>(c->scene.ds.lightPre), c->scene.numLights, (const float *)w.sums + 1);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hLightSums, w.sums, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->hLightSums.p, w.sums, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->evLights, c->stream));
-    c->lightsPending = true;
+    c->scene.lightsPending = true;
     return RDH_OK;
 }
 
 long long rdh_debug_read_lights(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
     if (int rc = settleLights(c)) return rc;
     long long bytes;
-    if (which == 0) bytes = (long long)sizeof(AliasRec) * c->ds.lightSamplerLength;
+    if (which == 0) bytes = (long long)sizeof(AliasRec) * c->scene.ds.lightSamplerLength;
     else if (which == 1) bytes = 16;
-    else if (which == 2) bytes = (long long)sizeof(LightPre) * c->numLights;
-    else if (which == 4) bytes = (long long)sizeof(int32_t) * c->numLights;  // (3 stays refused)
+    else if (which == 2) bytes = (long long)sizeof(LightPre) * c->scene.numLights;
+    else if (which == 4) bytes = (long long)sizeof(int32_t) * c->scene.numLights;  // (3 stays refused)
     else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lights: which = %d", which);
     if (!hostOut) return bytes;
     if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lights: %lld bytes needed", bytes);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->listEdited && c->numLights > 0) {  // the compaction's own total against the host's sum (rdh_scene_set_materials)
+    if (c->scene.listEdited && c->scene.numLights > 0) {  // the compaction's own total against the host's sum (rdh_scene_set_materials)
         int32_t total = 0;
         HIP_TRY(c, hipMemcpy(&total, emitWork(c->emitScratch).total, sizeof(total), hipMemcpyDeviceToHost));
-        if (total != c->numLights)
-            return fail(c, RDH_ERR_STATE, "rdh_debug_read_lights: the device counted %d emitters, the host %d", total, c->numLights);
+        if (total != c->scene.numLights)
+            return fail(c, RDH_ERR_STATE, "rdh_debug_read_lights: the device counted %d emitters, the host %d", total, c->scene.numLights);
     }
-    if (which == 0 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.lightAlias, bytes, hipMemcpyDeviceToHost));
-    else if (which == 2 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->ds.lightPre, bytes, hipMemcpyDeviceToHost));
-    else if (which == 4 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->dLightPrims, bytes, hipMemcpyDeviceToHost));
+    if (which == 0 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->scene.ds.lightAlias, bytes, hipMemcpyDeviceToHost));
+    else if (which == 2 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->scene.ds.lightPre, bytes, hipMemcpyDeviceToHost));
+    else if (which == 4 && bytes) HIP_TRY(c, hipMemcpy(hostOut, c->scene.dLightPrims, bytes, hipMemcpyDeviceToHost));
     else if (which == 1) {
-        const float f[2] = {1.f / c->ds.sumLightPowerInv, c->ds.sumLightPowerInv};
-        const int32_t n[2] = {c->ds.lightSamplerLength, c->numLights};
+        const float f[2] = {1.f / c->scene.ds.sumLightPowerInv, c->scene.ds.sumLightPowerInv};
+        const int32_t n[2] = {c->scene.ds.lightSamplerLength, c->scene.numLights};
         memcpy(hostOut, f, 8);
         memcpy(static_cast<char *>(hostOut) + 8, n, 8);
     }
@@ -3054,39 +3061,38 @@ namespace {
 
 static_assert(sizeof(rdh_object_range) == sizeof(PoseRange), "rdh_object_range layout");
 
-// Frees the table, the rest pose and the world arrays (scene allocations) of a scene that stays.
-int dropObjects(rdh_ctx *c) {
-    if (c->objects.empty()) return RDH_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // a pose or the update that followed it may still read them
-    const void *parts[] = {c->pose.objects, c->pose.restVertices, c->pose.restNormals, c->pose.worldVertices, c->pose.worldNormals};
-    for (const void *p : parts) {
-        auto it = std::find(c->sceneAllocs.begin(), c->sceneAllocs.end(), p);
-        if (it == c->sceneAllocs.end()) continue;
-        c->sceneAllocs.erase(it);
-        HIP_TRY(c, hipFree(const_cast<void *>(p)));
-    }
-    c->objects.clear();
-    c->pose = PoseArgs{};
-    c->worldStale = false;
-    return RDH_OK;
+// Frees the table, the rest pose and the world arrays (scene allocations) that `a` names.
+int freePoseArrays(rdh_ctx *c, PoseArgs &a, bool quiet = false) {
+    int rc = RDH_OK;
+    auto drop = [&](auto *slot) {
+        if (int e = sceneRelease(c, slot, quiet)) rc = rc ? rc : e;
+    };
+    drop(&a.objects);
+    drop(&a.restVertices);
+    drop(&a.restNormals);
+    drop(&a.worldVertices);
+    drop(&a.worldNormals);
+    return rc;
 }
 
-template <typename T>
-int sceneAlloc(rdh_ctx *c, T **out, size_t bytes) {
-    void *p = nullptr;
-    HIP_TRY(c, hipMalloc(&p, std::max<size_t>(bytes, 16)));
-    c->sceneAllocs.push_back(p);
-    *out = static_cast<T *>(p);
+// ... those of a scene that stays.
+int dropObjects(rdh_ctx *c) {
+    if (c->scene.objects.empty()) return RDH_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // a pose or the update that followed it may still read them
+    if (int rc = freePoseArrays(c, c->scene.pose)) return rc;
+    c->scene.objects.clear();
+    c->scene.pose = PoseArgs{};
+    c->scene.worldStale = false;
     return RDH_OK;
 }
 
 // The world arrays as the records hold them, on the context's stream.
 int seedWorld(rdh_ctx *c) {
-    const int N = c->ds.numPrims;
-    hipLaunchKernelGGL(k_pose_seed, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, c->ds.tris, c->ds.attrs, N,
-                       reinterpret_cast<float *>(c->pose.worldVertices), reinterpret_cast<float *>(c->pose.worldNormals));
+    const int N = c->scene.ds.numPrims;
+    hipLaunchKernelGGL(k_pose_seed, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.tris, c->scene.ds.attrs, N,
+                       reinterpret_cast<float *>(c->scene.pose.worldVertices), reinterpret_cast<float *>(c->scene.pose.worldNormals));
     HIP_TRY(c, hipGetLastError());
-    c->worldStale = false;
+    c->scene.worldStale = false;
     return RDH_OK;
 }
 
@@ -3097,13 +3103,13 @@ extern "C" {
 int rdh_scene_set_objects(rdh_ctx *c, const rdh_object_range *objects, int32_t numObjects, const float *restVertices,
                           const float *restNormals, int32_t numRestPrims) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_objects: no scene uploaded");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_objects: no scene uploaded");
     if (numObjects < 0) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_objects: numObjects %d", numObjects);
     HIP_TRY(c, hipSetDevice(c->device));
     if (numObjects == 0) return dropObjects(c);
     if (!objects || !restVertices || !restNormals || numRestPrims <= 0)
         return fail(c, RDH_ERR_ARGS, "rdh_scene_set_objects: null table or rest pose");
-    const int N = c->ds.numPrims;
+    const int N = c->scene.ds.numPrims;
     std::vector<std::pair<int, int>> spans;  // {firstPrim, end} of the objects that have triangles
     for (int i = 0; i < numObjects; i++) {
         const rdh_object_range &o = objects[i];
@@ -3124,89 +3130,68 @@ int rdh_scene_set_objects(rdh_ctx *c, const rdh_object_range *objects, int32_t n
     const size_t restBytes = sizeof(PoseVec) * 3 * (size_t)numRestPrims, worldBytes = sizeof(PoseVec) * 3 * (size_t)N;
     // built aside and committed only when every step went through: a failure leaves the scene without a table and frees its parts
     PoseArgs a{};
-    PoseRange *dObjects = nullptr;
-    PoseVec *restV = nullptr, *restN = nullptr;
-    const size_t allocsBefore = c->sceneAllocs.size();
     auto build = [&]() -> int {
-        if (int e = sceneAlloc(c, &dObjects, sizeof(PoseRange) * (size_t)numObjects)) return e;
-        if (int e = sceneAlloc(c, &restV, restBytes)) return e;
-        if (int e = sceneAlloc(c, &restN, restBytes)) return e;
+        if (int e = sceneAlloc(c, &a.objects, sizeof(PoseRange) * (size_t)numObjects)) return e;
+        if (int e = sceneAlloc(c, &a.restVertices, restBytes)) return e;
+        if (int e = sceneAlloc(c, &a.restNormals, restBytes)) return e;
         if (int e = sceneAlloc(c, &a.worldVertices, worldBytes)) return e;
         if (int e = sceneAlloc(c, &a.worldNormals, worldBytes)) return e;
-        HIP_TRY(c, hipMemcpy(dObjects, objects, sizeof(PoseRange) * (size_t)numObjects, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(restV, restVertices, restBytes, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(restN, restNormals, restBytes, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(const_cast<PoseRange *>(a.objects), objects, sizeof(PoseRange) * (size_t)numObjects, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(const_cast<PoseVec *>(a.restVertices), restVertices, restBytes, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(const_cast<PoseVec *>(a.restNormals), restNormals, restBytes, hipMemcpyHostToDevice));
         return RDH_OK;
     };
     if ((rc = build())) {
-        while (c->sceneAllocs.size() > allocsBefore) {
-            hipFree(c->sceneAllocs.back());
-            c->sceneAllocs.pop_back();
-        }
+        freePoseArrays(c, a, true);  // rc's text stays
         return rc;
     }
-    a.objects = dObjects;
-    a.restVertices = restV;
-    a.restNormals = restN;
-    c->pose = a;
-    c->objects.assign(objects, objects + numObjects);
-    c->objectStamp.assign((size_t)numObjects, 0u);
-    c->poseEpoch = 0;
+    c->scene.pose = a;
+    c->scene.objects.assign(objects, objects + numObjects);
+    c->scene.posed.reset((size_t)numObjects);
     return seedWorld(c);
 }
 
 int rdh_scene_pose_objects(rdh_ctx *c, const int32_t *objectIds, const float *xforms32, int32_t count, int tree, uint32_t flags,
                            float envPower) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene || c->objects.empty())
+    if (!c->scene.haveScene || c->scene.objects.empty())
         return fail(c, RDH_ERR_STATE, "rdh_scene_pose_objects: the scene has no object table (rdh_scene_set_objects)");
     if (tree != RDH_POSE_REFIT && tree != RDH_POSE_SAH && tree != RDH_POSE_LBVH)
         return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: unknown tree %d", tree);
     if (flags & ~RDH_POSE_REBUILD_LIGHTS) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: unknown flags %u", flags);
     if (count < 0 || (count > 0 && (!objectIds || !xforms32))) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: bad arguments");
-    if ((flags & RDH_POSE_REBUILD_LIGHTS) && c->ds.envTex >= 0 && !(envPower >= 0.f && envPower <= FLT_MAX))  // as rdh_scene_rebuild_lights
-        return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: envPower %g must be finite and not negative", (double)envPower);
+    int rc;
+    if ((flags & RDH_POSE_REBUILD_LIGHTS) && (rc = checkEnvPower(c, "rdh_scene_pose_objects", envPower))) return rc;
     if (count == 0) return RDH_OK;
-    if (++c->poseEpoch == 0) {  // the stamps have wrapped
-        std::fill(c->objectStamp.begin(), c->objectStamp.end(), 0u);
-        c->poseEpoch = 1;
-    }
-    const int numObjects = (int)c->objects.size();
+    c->scene.posed.beginCall();
+    const int numObjects = (int)c->scene.objects.size();
     for (int j = 0; j < count; j++) {
         const int id = objectIds[j];
         if (id < 0 || id >= numObjects) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: object id %d of %d", id, numObjects);
-        if (c->objectStamp[(size_t)id] == c->poseEpoch) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: object %d is listed twice", id);
-        c->objectStamp[(size_t)id] = c->poseEpoch;
+        if (!c->scene.posed.mark((size_t)id)) return fail(c, RDH_ERR_ARGS, "rdh_scene_pose_objects: object %d is listed twice", id);
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensureTreeHeader(c);
-    if (rc) return rc;
-    if (!c->evPoseStage[0])
-        for (int k = 0; k < 2; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->evPoseStage[k], hipEventDisableTiming));
+    if ((rc = ensureTreeHeader(c))) return rc;
 
-    // ids, transforms and the prefix sum of the listed objects' workgroup counts, through pinned memory: no host wait except for
-    // the copy of two poses ago (long done, normally)
-    const int s = c->poseStageNext;
+    // ids, transforms and the prefix sum of the listed objects' workgroup counts, through pinned memory: no host wait
     const size_t stageBytes = sizeof(int) * (2 * (size_t)count + 1) + sizeof(float) * 32 * (size_t)count;
-    HIP_TRY(c, hipEventSynchronize(c->evPoseStage[s]));
-    if ((rc = grow(c, c->hPoseStage[s], (size_t)count, stageBytes, Busy::Nothing))) return rc;
+    int *hPrefix = nullptr;
+    if ((rc = stageTake(c, c->poseStage, (size_t)count, stageBytes, &hPrefix))) return rc;
     if ((rc = grow(c, c->dPoseStage, (size_t)count, stageBytes, Busy::Stream))) return rc;
-    c->poseStageNext ^= 1;
-    int *hPrefix = c->hPoseStage[s].as<int>(), *hIds = hPrefix + count + 1;
+    int *hIds = hPrefix + count + 1;
     float *hXf = reinterpret_cast<float *>(hIds + count);
     long long groups = 0;
     for (int j = 0; j < count; j++) {
         hPrefix[j] = (int)groups;
-        groups += poseGroups(c->objects[(size_t)objectIds[j]].numPrims);  // at most 3 N / 256 + count in all: the ranges are disjoint
+        groups += poseGroups(c->scene.objects[(size_t)objectIds[j]].numPrims);  // at most 3 N / 256 + count in all: the ranges are disjoint
     }
     hPrefix[count] = (int)groups;
     memcpy(hIds, objectIds, sizeof(int) * (size_t)count);
     memcpy(hXf, xforms32, sizeof(float) * 32 * (size_t)count);
 
-    if (c->worldStale && (rc = seedWorld(c))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->dPoseStage.p, c->hPoseStage[s].p, stageBytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(c->evPoseStage[s], c->stream));
-    PoseArgs a = c->pose;
+    if (c->scene.worldStale && (rc = seedWorld(c))) return rc;
+    if ((rc = stageSend(c, c->poseStage, c->dPoseStage.p, stageBytes))) return rc;
+    PoseArgs a = c->scene.pose;
     a.prefix = c->dPoseStage.as<int>();
     a.ids = a.prefix + count + 1;
     a.xforms = reinterpret_cast<const float *>(a.ids + count);
@@ -3217,30 +3202,30 @@ int rdh_scene_pose_objects(rdh_ctx *c, const int32_t *objectIds, const float *xf
     }
 
     // the world arrays go where a caller's arrays go
-    const float *wv = reinterpret_cast<const float *>(c->pose.worldVertices), *wn = reinterpret_cast<const float *>(c->pose.worldNormals);
+    const float *wv = reinterpret_cast<const float *>(c->scene.pose.worldVertices), *wn = reinterpret_cast<const float *>(c->scene.pose.worldNormals);
     if (tree == RDH_POSE_REFIT) rc = rdh_scene_refit_geometry(c, wv, wn, nullptr);
     else rc = updateGeometry(c, wv, wn, nullptr, tree == RDH_POSE_LBVH ? RDH_BVH_LBVH : RDH_BVH_SAH, "rdh_scene_pose_objects");
     if (rc) {
-        c->worldStale = true;  // the records did not follow the arrays: seed them again before the next pose
+        c->scene.worldStale = true;  // the records did not follow the arrays: seed them again before the next pose
         return rc;
     }
-    c->worldStale = false;
+    c->scene.worldStale = false;
     if (flags & RDH_POSE_REBUILD_LIGHTS) return rdh_scene_rebuild_lights(c, envPower);
     return RDH_OK;
 }
 
 int rdh_debug_read_world(rdh_ctx *c, float *verticesOut, float *normalsOut) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene || c->objects.empty())
+    if (!c->scene.haveScene || c->scene.objects.empty())
         return fail(c, RDH_ERR_STATE, "rdh_debug_read_world: the scene has no object table (rdh_scene_set_objects)");
     if (!verticesOut || !normalsOut) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_world: null output");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->worldStale)
+    if (c->scene.worldStale)
         if (int rc = seedWorld(c)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t bytes = sizeof(PoseVec) * 3 * (size_t)c->ds.numPrims;
-    HIP_TRY(c, hipMemcpy(verticesOut, c->pose.worldVertices, bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(normalsOut, c->pose.worldNormals, bytes, hipMemcpyDeviceToHost));
+    const size_t bytes = sizeof(PoseVec) * 3 * (size_t)c->scene.ds.numPrims;
+    HIP_TRY(c, hipMemcpy(verticesOut, c->scene.pose.worldVertices, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(normalsOut, c->scene.pose.worldNormals, bytes, hipMemcpyDeviceToHost));
     return RDH_OK;
 }
 
@@ -3249,45 +3234,23 @@ int rdh_debug_read_world(rdh_ctx *c, float *verticesOut, float *normalsOut) {
 // ---- materials edited on the device (kernels_materials.h) -------------------------------------------------------------
 namespace {
 
-// A scene allocation replaced by one of `bytes`; the caller has made sure nothing still reads the old one.
-template <typename T>
-int replaceSceneAlloc(rdh_ctx *c, T **slot, size_t bytes) {
-    void *p = nullptr;
-    HIP_TRY(c, hipMalloc(&p, std::max<size_t>(bytes, 64)));
-    auto it = std::find(c->sceneAllocs.begin(), c->sceneAllocs.end(), static_cast<const void *>(*slot));
-    if (it != c->sceneAllocs.end()) {
-        hipFree(*it);
-        *it = p;
-    } else {
-        c->sceneAllocs.push_back(p);
-    }
-    *slot = static_cast<T *>(p);
-    return RDH_OK;
-}
-
 // Room for numLights emitters and a sampler of len entries.  Exceeding what the scene holds reallocates, which waits for every
 // stream that reads the old arrays; their contents are not kept (the caller rewrites all of them).  Shrinking frees nothing.
 int growLightArrays(rdh_ctx *c, int numLights, int len) {
-    if (numLights <= c->lightCap && len <= c->lightLenCap) return RDH_OK;
+    if (numLights <= c->scene.lightCap && len <= c->scene.lightLenCap) return RDH_OK;
     if (int rc = waitSideStreams(c)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (numLights > c->lightCap) {
-        LightRec *lights = const_cast<LightRec *>(c->ds.lights);
-        LightPre *pre = const_cast<LightPre *>(c->ds.lightPre);
-        if (int rc = replaceSceneAlloc(c, &lights, sizeof(LightRec) * (size_t)numLights)) return rc;
-        c->ds.lights = lights;
-        if (int rc = replaceSceneAlloc(c, &pre, sizeof(LightPre) * (size_t)numLights)) return rc;
-        c->ds.lightPre = pre;
-        if (int rc = replaceSceneAlloc(c, &c->dLightPrims, sizeof(int) * (size_t)numLights)) return rc;
-        c->lightCap = numLights;
+    if (numLights > c->scene.lightCap) {
+        if (int rc = sceneReplace(c, &c->scene.ds.lights, sizeof(LightRec) * (size_t)numLights)) return rc;
+        if (int rc = sceneReplace(c, &c->scene.ds.lightPre, sizeof(LightPre) * (size_t)numLights)) return rc;
+        if (int rc = sceneReplace(c, &c->scene.dLightPrims, sizeof(int) * (size_t)numLights)) return rc;
+        c->scene.lightCap = numLights;
     }
-    if (len > c->lightLenCap) {
-        AliasRec *alias = const_cast<AliasRec *>(c->ds.lightAlias);
-        if (int rc = replaceSceneAlloc(c, &alias, sizeof(AliasRec) * (size_t)len)) return rc;
-        c->ds.lightAlias = alias;
-        if (c->lightScratch)  // (a scene that was never rebuilt gets its scratch from the first rebuild, at the capacity of then)
-            if (int rc = replaceSceneAlloc(c, &c->lightScratch, aliasWorkBytes(len))) return rc;
-        c->lightLenCap = len;
+    if (len > c->scene.lightLenCap) {
+        if (int rc = sceneReplace(c, &c->scene.ds.lightAlias, sizeof(AliasRec) * (size_t)len)) return rc;
+        if (c->scene.lightScratch)  // (a scene that was never rebuilt gets its scratch from the first rebuild, at the capacity of then)
+            if (int rc = sceneReplace(c, &c->scene.lightScratch, aliasWorkBytes(len))) return rc;
+        c->scene.lightLenCap = len;
     }
     return RDH_OK;
 }
@@ -3323,91 +3286,80 @@ int rdh_build_light_list_device(rdh_ctx *c, const float *d_vertices, const int32
 
 int rdh_scene_set_materials(rdh_ctx *c, const int32_t *materialIds, const void *materials, int32_t count, float envPower) {
     if (!c) return RDH_ERR_ARGS;
-    if (!c->haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_materials: no scene uploaded");
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_materials: no scene uploaded");
     if (count < 0 || (count > 0 && (!materialIds || !materials))) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: bad arguments");
-    const bool hasEnv = c->ds.envTex >= 0;
-    if (hasEnv && !(envPower >= 0.f && envPower <= FLT_MAX))  // as rdh_scene_rebuild_lights
-        return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: envPower %g must be finite and not negative", (double)envPower);
+    int rc = checkEnvPower(c, "rdh_scene_set_materials", envPower);
+    if (rc) return rc;
     if (count == 0) return RDH_OK;
     const HostMaterial *hm = static_cast<const HostMaterial *>(materials);
-    const int numMaterials = (int)c->hostMats.size();
-    if (++c->matEpoch == 0) {  // the stamps have wrapped
-        std::fill(c->matStamp.begin(), c->matStamp.end(), 0u);
-        c->matEpoch = 1;
-    }
+    const int numMaterials = (int)c->scene.hostMats.size();
+    StampSet &listed = c->scene.edited;
+    listed.beginCall();
     bool relist = false;  // the set of Light materials, or a Light's colour, changes: the list and its LightRecs are derived again
     for (int j = 0; j < count; j++) {
         const int id = materialIds[j];
         if (id < 0 || id >= numMaterials) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: material id %d of %d", id, numMaterials);
-        if (c->matStamp[(size_t)id] == c->matEpoch) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: material %d is listed twice", id);
-        c->matStamp[(size_t)id] = c->matEpoch;
+        if (!listed.mark((size_t)id)) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: material %d is listed twice", id);
         for (int k = 0; k < 4; k++)
-            if (!mapIdValid(hm[j].map[k], k, c->numTextures))
+            if (!mapIdValid(hm[j].map[k], k, c->scene.numTextures))
                 return fail(c, RDH_ERR_ARGS, "rdh_scene_set_materials: material %d: map id %d out of range (numTextures %d)", id,
-                            hm[j].map[k], c->numTextures);
-        const HostMaterial &old = c->hostMats[(size_t)id];
+                            hm[j].map[k], c->scene.numTextures);
+        const HostMaterial &old = c->scene.hostMats[(size_t)id];
         const bool was = old.type == kMaterialLight, is = hm[j].type == kMaterialLight;
         if (was != is || (is && memcmp(old.color, hm[j].color, sizeof(old.color)) != 0)) relist = true;
     }
-    int numLights = c->numLights;
+    int numLights = c->scene.numLights;
     if (relist) {  // the count after the edit, without the device: a host sum over the materials as they will stand
         long long n = 0;
         for (int i = 0; i < numMaterials; i++)
-            if (c->hostMats[(size_t)i].type == kMaterialLight && c->matStamp[(size_t)i] != c->matEpoch) n += c->matPrims[(size_t)i];
+            if (c->scene.hostMats[(size_t)i].type == kMaterialLight && !listed.marked((size_t)i)) n += c->scene.matPrims[(size_t)i];
         for (int j = 0; j < count; j++)
-            if (hm[j].type == kMaterialLight) n += c->matPrims[(size_t)materialIds[j]];
+            if (hm[j].type == kMaterialLight) n += c->scene.matPrims[(size_t)materialIds[j]];
         numLights = (int)n;
     }
-    const int len = numLights + (hasEnv ? 1 : 0);
-    const int N = c->ds.numPrims;
+    const int len = numLights + (c->scene.ds.envTex >= 0 ? 1 : 0);
+    const int N = c->scene.ds.numPrims;
 
     // everything that can fail for want of memory comes before the scene is touched
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensureTreeHeader(c);
-    if (rc) return rc;
-    if (!c->evMatStage[0])
-        for (int k = 0; k < 2; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->evMatStage[k], hipEventDisableTiming));
-    const int s = c->matStageNext;
+    if ((rc = ensureTreeHeader(c))) return rc;
     const size_t stageBytes = (sizeof(MatRec) + sizeof(int)) * (size_t)count;
-    HIP_TRY(c, hipEventSynchronize(c->evMatStage[s]));  // the copy of two edits ago (long done, normally)
-    if ((rc = grow(c, c->hMatStage[s], (size_t)count, stageBytes, Busy::Nothing))) return rc;
+    MatRec *hRecs = nullptr;
+    if ((rc = stageTake(c, c->matStage, (size_t)count, stageBytes, &hRecs))) return rc;
     if ((rc = grow(c, c->dMatStage, (size_t)count, stageBytes, Busy::Stream))) return rc;
     EmitWork w{};
     if ((rc = growEmitWork(c, N, &w))) return rc;
     if (relist && (rc = growLightArrays(c, numLights, len))) return rc;
-    c->matStageNext ^= 1;
 
-    MatRec *hRecs = c->hMatStage[s].as<MatRec>();
     int *hIds = reinterpret_cast<int *>(hRecs + count);
     for (int j = 0; j < count; j++) {
         hRecs[j] = toMatRec(hm[j]);
         hIds[j] = materialIds[j];
-        c->hostMats[(size_t)materialIds[j]] = hm[j];
+        c->scene.hostMats[(size_t)materialIds[j]] = hm[j];
     }
     if ((rc = waitSideStreams(c))) return rc;  // the records are rewritten in place
-    HIP_TRY(c, hipMemcpyAsync(c->dMatStage.p, c->hMatStage[s].p, stageBytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(c->evMatStage[s], c->stream));
+    if ((rc = stageSend(c, c->matStage, c->dMatStage.p, stageBytes))) return rc;
     const MatRec *dRecs = c->dMatStage.as<MatRec>();
     hipLaunchKernelGGL(k_mat_write, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, dRecs,
-                       reinterpret_cast<const int *>(dRecs + count), count, const_cast<MatRec *>(c->ds.mats));
+                       reinterpret_cast<const int *>(dRecs + count), count, const_cast<MatRec *>(c->scene.ds.mats));
     const unsigned blocks = (unsigned)((N + 255) / 256);
-    const SceneEmitters ld{c->ds.tris, c->ds.mats, const_cast<unsigned char *>(c->ds.primClass), c->dLightPrims,
-                           const_cast<LightRec *>(c->ds.lights), numLights};
+    const SceneEmitters ld{c->scene.ds.tris, c->scene.ds.mats, const_cast<unsigned char *>(c->scene.ds.primClass), c->scene.dLightPrims,
+                           const_cast<LightRec *>(c->scene.ds.lights), numLights};
     hipLaunchKernelGGL(k_emit_count_scene, dim3(blocks), dim3(256), 0, c->stream, ld, N, w.blockTotals);  // primClass rides here
     HIP_TRY(c, hipGetLastError());
     if (!relist) return RDH_OK;
 
-    c->numLights = numLights;
-    c->ds.lightSamplerLength = len;  // at once: the length never waits for the device
+    c->scene.numLights = numLights;
+    c->scene.ds.lightSamplerLength = len;  // at once: the length never waits for the device
     if (numLights > 0) {
         hipLaunchKernelGGL(k_emit_scan, dim3(1), dim3(256), 0, c->stream, w.blockTotals, (int)blocks, (const int *)nullptr, w.total);
         hipLaunchKernelGGL(k_emit_scatter_scene, dim3(blocks), dim3(256), 0, c->stream, ld, N, (const int *)w.blockTotals);
         HIP_TRY(c, hipGetLastError());
-        c->listEdited = true;
+        c->scene.listEdited = true;
     }
     if (len == 0) {  // nothing to sample: what an upload of a scene without lights holds; a rebuild still in flight is dropped
-        c->ds.sumLightPowerInv = 0.f;
-        c->lightsPending = false;
+        c->scene.ds.sumLightPowerInv = 0.f;
+        c->scene.lightsPending = false;
         return RDH_OK;
     }
     return rdh_scene_rebuild_lights(c, envPower);
