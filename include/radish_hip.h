@@ -307,7 +307,7 @@ int rdh_debug_read_world(rdh_ctx *ctx, float *verticesOut, float *normalsOut);
  * before anything is enqueued, the scene unchanged: no scene RDH_ERR_NO_SCENE; an id out of range or listed twice, null pointers
  * with count > 0, a map id rdh_scene_upload would refuse (it must name one of the uploaded textures, -1, or -2 for a base
  * colour), an envPower rdh_scene_rebuild_lights would refuse: RDH_ERR_ARGS.  count == 0: RDH_OK, nothing enqueued.
- * Out of scope: giving triangles other material ids, and editing textures; both still take rdh_scene_upload.
+ * Out of scope: giving triangles other material ids, which still takes rdh_scene_upload (textures: rdh_scene_set_texture, below).
  * rdh_build_light_list_device: the device twin of rdh_build_light_list (include/radish_host.h) — d_vertices float[3*numPrims][3],
  * d_materialIds int32[numPrims], d_materials Material[numMaterials] -> d_lightPrimIds int32[], d_lightUnitRadiance float[][3],
  * d_lightPower float[] (each with room for numPrims entries; the first *d_count are written) and *d_count, bit for bit what the
@@ -318,6 +318,37 @@ int rdh_scene_set_materials(rdh_ctx *ctx, const int32_t *materialIds, const void
 int rdh_build_light_list_device(rdh_ctx *ctx, const float *d_vertices, const int32_t *d_materialIds, int32_t numPrims,
                                 const void *d_materials, int32_t numMaterials, int32_t *d_lightPrimIds, float *d_lightUnitRadiance,
                                 float *d_lightPower, int32_t *d_count);
+/* ---- textures and the environment map edited on the device -------------------------------------------------------------
+ * A scene whose textures were edited here is, bit for bit, the scene a fresh rdh_scene_upload of the edited description gives (the
+ * alias tables' NaN payloads aside, as for rdh_build_alias_table_device).
+ * rdh_scene_set_texture: d_texels float[height][width][3] (DEVICE, row-major: the layout of rdh_texture::data) replaces the texels
+ * of texture texId of the uploaded scene in place; width and height must be the uploaded texture's (another size, another texture
+ * count or another environment map still take rdh_scene_upload).  Asynchronous on the context's stream, which orders the copy
+ * after the caller's writes to d_texels on that stream; no host wait.  A texture that is not the environment map: the copy and
+ * nothing else.  The environment map: the same call also derives, on the device, what rdh_build_envmap_pdf + rdh_build_alias_table
+ * (include/radish_host.h) and the upload derive from its texels — the pixel weights luminance * sin((0.5 + i) / height * PI), the
+ * pixel alias table over them, and their sum, the environment's power; then what rdh_scene_rebuild_lights does follows with that
+ * sum, read from device memory, as the light sampler's last entry: powers, alias table, per-light constants, sumLightPowerInv (which
+ * reaches the host as after a rebuild).  The row factors sin(...) are the host's (glibc's sinf, not the device's): the first
+ * environment edit of a scene computes them in the call and sends them through pinned memory, and allocates the workspace (20 B per
+ * pixel: 4 for the weights, 16 for the construction's two lists); later edits allocate and send nothing.  The construction is rdh_build_alias_
+ * table_device's: two single-wave kernels whose time grows linearly with width x height (measured: DESIGN 11h).  The tree, the
+ * pairs, the refit plan, the object table and world arrays, motion tracking, the persistent block order and the material copies
+ * are kept, and so are ReSTIR reservoirs: a caller who changes the environment should call rdh_restir_init, as after every other
+ * scene edit that changes the lights.  Checked before anything is enqueued, the scene unchanged: no scene RDH_ERR_NO_SCENE; texId
+ * outside [0, numTextures), a null pointer, a width or height that differs: RDH_ERR_ARGS.
+ * rdh_scene_env_power: *out = the power of the environment entry as the scene holds it: after an environment edit that edit's sum
+ * (the call waits for it); on a scene never edited the same kernels' sum over the uploaded texels, which has the bits of the sum
+ * rdh_build_alias_table returned when the scene was made.  This is the envPower to hand to a later rdh_scene_rebuild_lights,
+ * rdh_scene_set_materials or rdh_scene_pose_objects: a value kept from before an environment edit is stale.  Blocking.  No scene:
+ * RDH_ERR_NO_SCENE; a scene without an environment map: RDH_ERR_STATE; a null pointer: RDH_ERR_ARGS.
+ * rdh_debug_read_textures: test access: which = 0 every texture's texels as the kernels read them (texData, in upload order), 1 the
+ * environment map's alias table (envMapSamplerLength x 8 B), 2 {float envPower (rdh_scene_env_power's; 0 without an environment
+ * map); int32 envMapTexId, envMapSamplerLength, numTextures} (16 B).  Returns the byte size (hostOut NULL: only that) or a negative
+ * RDH_ERR_*.  Blocking. */
+int rdh_scene_set_texture(rdh_ctx *ctx, int32_t texId, const float *d_texels, int32_t width, int32_t height);
+int rdh_scene_env_power(rdh_ctx *ctx, float *out);
+long long rdh_debug_read_textures(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
 /* Replaces DevScene::destroy (src/scene.cpp:553-574). */
 int rdh_scene_free(rdh_ctx *ctx);
 /* The `Camera cam` kernel argument of every reference kernel (State::scene->camera, src/pathtrace.cu:356). */

@@ -73,6 +73,7 @@ EXPORTS = [
     "rdh_build_alias_table_device", "rdh_scene_rebuild_lights", "rdh_debug_read_lights",
     "rdh_scene_set_objects", "rdh_scene_pose_objects", "rdh_debug_read_world",
     "rdh_scene_set_materials", "rdh_build_light_list_device",
+    "rdh_scene_set_texture", "rdh_scene_env_power", "rdh_debug_read_textures",
 ]
 
 
@@ -207,6 +208,9 @@ def lib():
             "rdh_debug_read_world": ([vp, vp, vp], i32),
             "rdh_scene_set_materials": ([vp, vp, vp, i32, C.c_float], i32),
             "rdh_build_light_list_device": ([vp, vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
+            "rdh_scene_set_texture": ([vp, i32, vp, i32, i32], i32),
+            "rdh_scene_env_power": ([vp, C.POINTER(C.c_float)], i32),
+            "rdh_debug_read_textures": ([vp, i32, vp, i64], i64),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -480,6 +484,42 @@ class Context:
         self.check(lib().rdh_build_light_list_device(self.h, vp, ip, n, mp, m, prims.data_ptr() if n else None,
                                                      radiance.data_ptr() if n else None, power.data_ptr() if n else None, count.data_ptr()))
         return prims, radiance, power, count
+
+    # ---- textures and the environment map edited on the device ----
+    def set_texture(self, tex_id, texels):
+        """Replace the texels of texture tex_id of the uploaded scene (rdh_scene_set_texture): texels a float32 cuda tensor
+        [height, width, 3] of the uploaded texture's size.  When tex_id is the environment map, its pixel alias table, its power
+        and with it the light sampler (alias table, sumLightPowerInv, per-light constants) are derived again on the device.  The
+        scene then renders like a fresh upload_scene of the edited description.  Does not block."""
+        torch = _torch()
+        if not isinstance(texels, torch.Tensor) or texels.dim() != 3 or texels.shape[2] != 3:
+            raise RadishError("set_texture: texels must be a tensor [height, width, 3]")
+        h, w = int(texels.shape[0]), int(texels.shape[1])
+        self.check(lib().rdh_scene_set_texture(self.h, int(tex_id), self._ptr(texels, 3 * w * h, "set_texture texels"), w, h))
+
+    def env_power(self):
+        """The environment entry's power as the scene holds it, np.float32 (rdh_scene_env_power): SceneData.env_power of the scene
+        as it stands, also after set_texture changed the environment map.  The env_power argument of a later rebuild_lights,
+        set_materials or pose_objects.  Blocking; raises on a scene without an environment map."""
+        out = C.c_float(0)
+        self.check(lib().rdh_scene_env_power(self.h, C.byref(out)))
+        return np.float32(out.value)
+
+    def debug_read_textures(self, which):
+        """Blocking test access (rdh_debug_read_textures): 0 -> every texture's texels (float32, upload order), 1 -> the
+        environment map's alias table (layouts.BINOMIAL_DTYPE), 2 -> {float32 envPower; int32 envMapTexId, envMapSamplerLength,
+        numTextures} as 16 bytes."""
+        n = lib().rdh_debug_read_textures(self.h, which, None, 0)
+        if n < 0:
+            self.check(int(n))
+        out = np.zeros(n, np.uint8)
+        if n:
+            rc = lib().rdh_debug_read_textures(self.h, which, out.ctypes.data, n)
+            if rc < 0:
+                self.check(int(rc))
+        if which == 0:
+            return out.view(np.float32)
+        return out.view(L.BINOMIAL_DTYPE) if which == 1 else out
 
     # ---- moving geometry: objects posed on the device (DESIGN 11f) ----
     def set_objects(self, sd=None, objects=None, rest_vertices=None, rest_normals=None):

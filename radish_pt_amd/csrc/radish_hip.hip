@@ -35,6 +35,7 @@
 #include "device/kernels_lights.h"
 #include "device/kernels_pose.h"
 #include "device/kernels_materials.h"
+#include "device/kernels_textures.h"
 
 using namespace rd;
 
@@ -148,6 +149,14 @@ struct SceneState {
     int lightCap = 0;                    // emitters that ds.lights, ds.lightPre and dLightPrims hold (never shrink)
     int lightLenCap = 0;                 // entries that ds.lightAlias and lightScratch hold
     bool listEdited = false;             // an edit rebuilt the list: emitScratch holds the device's own total (rdh_debug_read_lights)
+
+    // rdh_scene_set_texture / rdh_scene_env_power (kernels_textures.h)
+    std::vector<int4> texInfo;           // host copy of ds.texInfo: {width, height, first texel, 0} of each uploaded texture
+    size_t texFloats = 0;                // floats of those textures in ds.texData
+    void *envScratch = nullptr;          // pixel weights + AliasWork laid out for envSamplerLength entries (made by the first environment
+                                         // edit, or by rdh_scene_env_power)
+    float *envRowSin = nullptr;          // the environment map's row factors, the host's sinf((.5f + i) / height * PI): sent once
+    bool envSumValid = false;            // envScratch's sums[0] is the power of the environment map as ds.texData holds it
 };
 
 struct rdh_ctx {
@@ -254,6 +263,9 @@ struct rdh_ctx {
     StagePair matStage{bufs};
     GrowBuf dMatStage{bufs};             // listed materials: where k_mat_write reads them
     GrowBuf emitScratch{bufs};           // 256-triangle blocks: the compaction's block totals, then {error flag, total}
+
+    // rdh_scene_set_texture (kernels_textures.h): the environment map's row factors on their way to SceneState::envRowSin
+    StagePair rowStage{bufs};
 };
 
 namespace {
@@ -1117,6 +1129,7 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
         texInfo[i] = make_int4(t.width, t.height, (int)(texBlob.size() / 3), 0);
         texBlob.insert(texBlob.end(), t.data, t.data + 3 * (size_t)t.width * t.height);
     }
+    const size_t texFloats = texBlob.size();
     if (texBlob.empty()) texBlob.assign(4, 0.f);
 
     const int N = d->numPrims, S = d->bvhSize;
@@ -1245,6 +1258,8 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
     for (int p = 0; p < N; p++) c->scene.matPrims[(size_t)d->materialIds[p]]++;
     c->scene.edited.reset((size_t)d->numMaterials);
     c->scene.numTextures = d->numTextures;
+    c->scene.texInfo.assign(texInfo.begin(), texInfo.begin() + d->numTextures);  // rdh_scene_set_texture checks sizes against these
+    c->scene.texFloats = texFloats;
     c->scene.haveScene = true;
     c->orderValid = false;
     return RDH_OK;
@@ -2976,6 +2991,40 @@ void launchAliasBuild(rdh_ctx *c, const float *d_values, int n, const AliasWork 
     hipLaunchKernelGGL(k_alias_sweep, dim3(1), dim3(64), 0, c->stream, w, d_table);
 }
 
+// What a light rebuild allocates: everything of it that can fail for want of memory, before the scene is touched.
+int prepareLightRebuild(rdh_ctx *c) {
+    int rc;
+    if ((rc = ensureTreeHeader(c))) return rc;
+    if ((rc = grow(c, c->hLightSums, 2, 2 * sizeof(float), Busy::Nothing))) return rc;
+    if (!c->evLights && (rc = newEvent(c, &c->evLights))) return rc;
+    if (!c->scene.lightScratch && (rc = sceneAlloc(c, &c->scene.lightScratch, aliasWorkBytes(c->scene.lightLenCap)))) return rc;
+    return RDH_OK;
+}
+
+// The light sampler again, on the context's stream (after prepareLightRebuild; lightSamplerLength > 0): powers, alias table, per-light
+// constants, and {sum, 1 / sum} on their way to the host (settleLights).  The environment entry's power is envPower, or, with
+// d_envPower, what that device address holds when the stream gets here (rdh_scene_set_texture).
+int enqueueLightRebuild(rdh_ctx *c, float envPower, const float *d_envPower) {
+    const int len = c->scene.ds.lightSamplerLength;
+    if (int rc = waitSideStreams(c)) return rc;  // the table and the per-light constants are rewritten in place
+    float *power = static_cast<float *>(c->scene.lightScratch);
+    const AliasWork w = lightWork(c->scene.lightScratch, c->scene.lightLenCap);  // laid out for the capacity (rdh_scene_set_materials changes len)
+    const dim3 grid((unsigned)((len + 255) / 256));
+    if (d_envPower)
+        hipLaunchKernelGGL(k_light_power_dev, grid, dim3(256), 0, c->stream, c->scene.ds.lights, c->scene.numLights, len, d_envPower, power);
+    else
+        hipLaunchKernelGGL(k_light_power, grid, dim3(256), 0, c->stream, c->scene.ds.lights, c->scene.numLights, len, envPower, power);
+    launchAliasBuild(c, power, len, w, const_cast<AliasRec *>(c->scene.ds.lightAlias));
+    if (c->scene.numLights > 0)
+        hipLaunchKernelGGL(k_light_precompute_dev, dim3((unsigned)((c->scene.numLights + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.lights,
+                           const_cast<LightPre *>(c->scene.ds.lightPre), c->scene.numLights, (const float *)w.sums + 1);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->hLightSums.p, w.sums, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(c->evLights, c->stream));
+    c->scene.lightsPending = true;
+    return RDH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2999,27 +3048,10 @@ int rdh_scene_rebuild_lights(rdh_ctx *c, float envPower) {
     if (!c->scene.haveScene) return fail(c, RDH_ERR_ARGS, "rdh_scene_rebuild_lights: no scene uploaded");
     int rc = checkEnvPower(c, "rdh_scene_rebuild_lights", envPower);
     if (rc) return rc;
-    const int len = c->scene.ds.lightSamplerLength;
-    if (len == 0) return RDH_OK;
+    if (c->scene.ds.lightSamplerLength == 0) return RDH_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensureTreeHeader(c))) return rc;
-    if ((rc = grow(c, c->hLightSums, 2, 2 * sizeof(float), Busy::Nothing))) return rc;
-    if (!c->evLights && (rc = newEvent(c, &c->evLights))) return rc;
-    if (!c->scene.lightScratch && (rc = sceneAlloc(c, &c->scene.lightScratch, aliasWorkBytes(c->scene.lightLenCap)))) return rc;
-    if ((rc = waitSideStreams(c))) return rc;  // the table and the per-light constants are rewritten in place
-    float *power = static_cast<float *>(c->scene.lightScratch);
-    const AliasWork w = lightWork(c->scene.lightScratch, c->scene.lightLenCap);  // laid out for the capacity (rdh_scene_set_materials changes len)
-    hipLaunchKernelGGL(k_light_power, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.lights, c->scene.numLights, len,
-                       envPower, power);
-    launchAliasBuild(c, power, len, w, const_cast<AliasRec *>(c->scene.ds.lightAlias));
-    if (c->scene.numLights > 0)
-        hipLaunchKernelGGL(k_light_precompute_dev, dim3((unsigned)((c->scene.numLights + 255) / 256)), dim3(256), 0, c->stream, c->scene.ds.lights,
-                           const_cast<LightPre *>(c->scene.ds.lightPre), c->scene.numLights, (const float *)w.sums + 1);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->hLightSums.p, w.sums, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipEventRecord(c->evLights, c->stream));
-    c->scene.lightsPending = true;
-    return RDH_OK;
+    if ((rc = prepareLightRebuild(c))) return rc;
+    return enqueueLightRebuild(c, envPower, nullptr);
 }
 
 long long rdh_debug_read_lights(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
@@ -3363,6 +3395,125 @@ int rdh_scene_set_materials(rdh_ctx *c, const int32_t *materialIds, const void *
         return RDH_OK;
     }
     return rdh_scene_rebuild_lights(c, envPower);
+}
+
+}  // extern "C"
+
+// ---- textures and the environment map edited on the device (kernels_textures.h) ----------------------------------------
+namespace {
+
+// The environment map's workspace, made by the first call that needs it: the pixel weights and the AliasWork of its pixels, and
+// the row factors, which depend on the map's height alone.  The host computes those with rdh_build_envmap_pdf's expression (glibc's
+// sinf is not the device's) and they go through pinned memory: no host wait beyond the copy of two calls ago.
+int ensureEnvWork(rdh_ctx *c) {
+    SceneState &s = c->scene;
+    const int n = s.ds.envSamplerLength, height = s.texInfo[(size_t)s.ds.envTex].y;
+    int rc;
+    if (!s.envScratch && (rc = sceneAlloc(c, &s.envScratch, aliasWorkBytes(n)))) return rc;
+    if (s.envRowSin) return RDH_OK;
+    const size_t bytes = sizeof(float) * (size_t)height;
+    float *host = nullptr, *dev = nullptr;
+    if ((rc = stageTake(c, c->rowStage, (size_t)height, bytes, &host))) return rc;
+    if ((rc = sceneAlloc(c, &dev, bytes))) return rc;
+    const float PI = 3.1415926535897932384626422832795028841971f;
+    for (int i = 0; i < height; i++) host[i] = sinf((.5f + i) / height * PI);
+    if ((rc = stageSend(c, c->rowStage, dev, bytes))) {
+        sceneRelease(c, &dev, true);
+        return rc;
+    }
+    s.envRowSin = dev;
+    return RDH_OK;
+}
+
+// texels -> pixel weights -> their sum in envScratch's sums[0], and with `table` the scene's envAlias, on the context's stream.
+void enqueueEnvSampler(rdh_ctx *c, bool table) {
+    SceneState &s = c->scene;
+    const int4 info = s.texInfo[(size_t)s.ds.envTex];
+    const int n = s.ds.envSamplerLength;
+    float *pdf = static_cast<float *>(s.envScratch);
+    const AliasWork w = lightWork(s.envScratch, n);
+    hipLaunchKernelGGL(k_env_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, s.ds.texData + 3 * (size_t)info.z,
+                       (const float *)s.envRowSin, info.x, n, pdf);
+    if (table) launchAliasBuild(c, pdf, n, w, const_cast<AliasRec *>(s.ds.envAlias));
+    else hipLaunchKernelGGL(k_alias_classify, dim3(1), dim3(64), 0, c->stream, (const float *)pdf, n, w);
+    s.envSumValid = true;
+}
+
+// The environment entry's power as the scene holds it (the scene has an environment map).  Blocking.
+int readEnvPower(rdh_ctx *c, float *out) {
+    if (!c->scene.envSumValid) {  // never edited: from the uploaded texels, with the kernels of an edit
+        if (int rc = ensureEnvWork(c)) return rc;
+        enqueueEnvSampler(c, false);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(out, lightWork(c->scene.envScratch, c->scene.ds.envSamplerLength).sums, sizeof(float), hipMemcpyDeviceToHost));
+    return RDH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rdh_scene_set_texture(rdh_ctx *c, int32_t texId, const float *d_texels, int32_t width, int32_t height) {
+    if (!c) return RDH_ERR_ARGS;
+    SceneState &s = c->scene;
+    if (!s.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_texture: no scene uploaded");
+    if (texId < 0 || texId >= s.numTextures) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_texture: texture id %d of %d", texId, s.numTextures);
+    if (!d_texels) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_texture: d_texels is null");
+    const int4 info = s.texInfo[(size_t)texId];
+    if (width != info.x || height != info.y)
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_set_texture: texture %d is %dx%d, not %dx%d (another size takes rdh_scene_upload)", texId,
+                    info.x, info.y, width, height);
+    const bool env = texId == s.ds.envTex;
+
+    // everything that can fail for want of memory comes before the scene is touched
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensureTreeHeader(c))) return rc;
+    if (env && ((rc = ensureEnvWork(c)) || (rc = prepareLightRebuild(c)))) return rc;
+
+    if ((rc = waitSideStreams(c))) return rc;  // the texels are rewritten in place
+    HIP_TRY(c, hipMemcpyAsync(const_cast<float *>(s.ds.texData) + 3 * (size_t)info.z, d_texels, sizeof(float) * 3 * (size_t)info.x * info.y,
+                              hipMemcpyDeviceToDevice, c->stream));
+    if (!env) return RDH_OK;
+    enqueueEnvSampler(c, true);
+    HIP_TRY(c, hipGetLastError());
+    return enqueueLightRebuild(c, 0.f, lightWork(s.envScratch, s.ds.envSamplerLength).sums);
+}
+
+int rdh_scene_env_power(rdh_ctx *c, float *out) {
+    if (!c || !out) return RDH_ERR_ARGS;
+    if (!c->scene.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_env_power: no scene uploaded");
+    if (c->scene.ds.envTex < 0) return fail(c, RDH_ERR_STATE, "rdh_scene_env_power: the scene has no environment map");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return readEnvPower(c, out);
+}
+
+long long rdh_debug_read_textures(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
+    if (!c) return RDH_ERR_ARGS;
+    const SceneState &s = c->scene;
+    if (!s.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    long long bytes;
+    if (which == 0) bytes = (long long)(sizeof(float) * s.texFloats);
+    else if (which == 1) bytes = (long long)sizeof(AliasRec) * s.ds.envSamplerLength;
+    else if (which == 2) bytes = 16;
+    else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_textures: which = %d", which);
+    if (!hostOut) return bytes;
+    if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_textures: %lld bytes needed", bytes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (which == 0 && bytes) HIP_TRY(c, hipMemcpy(hostOut, s.ds.texData, bytes, hipMemcpyDeviceToHost));
+    else if (which == 1 && bytes) HIP_TRY(c, hipMemcpy(hostOut, s.ds.envAlias, bytes, hipMemcpyDeviceToHost));
+    else if (which == 2) {
+        float envPower = 0.f;
+        if (s.ds.envTex >= 0)
+            if (int rc = readEnvPower(c, &envPower)) return rc;
+        const int32_t n[3] = {s.ds.envTex, s.ds.envSamplerLength, s.numTextures};
+        memcpy(hostOut, &envPower, 4);
+        memcpy(static_cast<char *>(hostOut) + 4, n, 12);
+    }
+    return bytes;
 }
 
 }  // extern "C"
