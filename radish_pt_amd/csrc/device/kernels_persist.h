@@ -9,7 +9,7 @@
 //
 // Every lane executes exactly singleKernelPT's sequence for its pixel (/root/reference/src/pathtrace.cu:149-291):
 // primary ray → [NEE sample → shadow ray → BSDF sample → extension ray]* with the same RNG draws and the same order of
-// additions, so the result is bit-identical to the megakernel and to the queue pipeline.  Wave-level scheduling only
+// additions (the bounce body is pathStep, path_step.h), so the result is bit-identical to the megakernel and to the queue pipeline.  Wave-level scheduling only
 // decides WHEN a lane's next step runs:
 //   box steps   while enough lanes are walking,
 //   leaf tests  when >= 1/RD_PT_LEAF_DEN of the tracing lanes are parked on a leaf,
@@ -281,24 +281,41 @@ __global__ __launch_bounds__(64, PAIRS && !COUNT ? RD_PERSIST_PAIR_WAVES : RD_PE
             else node = kPairFresh;  // a literal-class ray: traced whole below
         }
     };
-    auto startShadow = [&](v3 x, v3 y) {  // DevScene::testOcclusion's ray set-up (scene.h:304-311)
-        v3 dir = y - x;
-        float dist = length(dir);
-        dir = dir / dist;
+    auto startShadow = [&](v3 x, v3 y) {
+        float limit;
+        const Ray ray = shadowRay(x, y, limit);
         nAny++;
-        startTrace(makeOffsetedRay(x, dir), dist - 1e-4f, true);
+        startTrace(ray, limit, true);
     };
     auto finishPixel = [&]() {  // pathtrace.cu:279-290
-        v3 direct = mk3(sAccD[0][t], sAccD[1][t], sAccD[2][t]);
-        v3 indirect = mk3(sAccI[0][t], sAccI[1][t], sAccI[2][t]);
-        if (hasNanOrInf(direct)) direct = mk3(0.f);
-        if (hasNanOrInf(indirect)) indirect = mk3(0.f);
-        direct = HDRToLDR(direct);
-        indirect = HDRToLDR(indirect);
-        storeRunningMean(directIllum, outIdx, direct, iter);
-        storeRunningMean(indirectIllum, outIdx, indirect, iter);
+        storeRunningMean(directIllum, outIdx, finishSample(mk3(sAccD[0][t], sAccD[1][t], sAccD[2][t])), iter);
+        storeRunningMean(indirectIllum, outIdx, finishSample(mk3(sAccI[0][t], sAccI[1][t], sAccI[2][t])), iter);
         atomicMax(&blockCost[myBlock], pathSteps);
         state = PS_IDLE;
+    };
+    // this lane's path state as pathStep sees it (path_step.h): column t of the LDS arrays, the sampler's state in registers
+    struct LanePath {
+        const int t;
+        uint32_t &scramble;
+        int &ptr;
+        RD_DEV v3 throughput() const { return mk3(sThr[0][t], sThr[1][t], sThr[2][t]); }
+        RD_DEV float samplePdf() const { return sExtPdf[t]; }
+        RD_DEV bool sampleDelta() const { return (sFlags[t] & 2) != 0; }
+        RD_DEV v3 prevPos() const { return mk3(sCur[0][t], sCur[1][t], sCur[2][t]); }
+        RD_DEV void setDirect(v3 v) { sAccD[0][t] = v.x; sAccD[1][t] = v.y; sAccD[2][t] = v.z; }
+        RD_DEV void addIndirect(v3 v) { sAccI[0][t] += v.x; sAccI[1][t] += v.y; sAccI[2][t] += v.z; }
+        RD_DEV Sampler rng(const DScene &sc) const { return Sampler{sc.sobol, scramble, ptr}; }
+        RD_DEV void setNee(v3 c, float w) { sNee[0][t] = c.x; sNee[1][t] = c.y; sNee[2][t] = c.z; sNee[3][t] = w; }
+        RD_DEV void setPrevPos(v3 x) { sCur[0][t] = x.x; sCur[1][t] = x.y; sCur[2][t] = x.z; }
+        RD_DEV void setRay(const Ray &ray, float pdf, bool delta, v3 throughput, const Sampler &rng) {
+            sExtO[0][t] = ray.o.x; sExtO[1][t] = ray.o.y; sExtO[2][t] = ray.o.z;
+            sExtD[0][t] = ray.d.x; sExtD[1][t] = ray.d.y; sExtD[2][t] = ray.d.z;
+            sExtPdf[t] = pdf;
+            sThr[0][t] = throughput.x; sThr[1][t] = throughput.y; sThr[2][t] = throughput.z;
+            sFlags[t] = 1 | (delta ? 2 : 0);
+            scramble = rng.scramble;
+            ptr = rng.ptr;
+        }
     };
     auto startExtensionOrFinish = [&]() {
         if (sFlags[t] & 1) {
@@ -545,101 +562,17 @@ __global__ __launch_bounds__(64, PAIRS && !COUNT ? RD_PERSIST_PAIR_WAVES : RD_PE
             if (__popcll(shadeM) * 64 >= nBusy * (exhausted ? RD_SHADE_MIN_DRAIN : RD_SHADE_MIN)) {
                 PH_COUNT(12, shadeM);
                 if (state == PS_SHADE) {
-                    v3 rayDir = rayD;
-                    bool terminate = true;  // set false once a shadow or extension ray is started
-                    do {
-                        if (hitPrim == -1) {  // miss: pathtrace.cu:169-172 (primary), :232-247 (later)
-                            if (k == 0) {
-                                sAccD[0][t] = sAccD[1][t] = sAccD[2][t] = 1.f;
-                            } else if (hasEnvMap(s)) {
-                                v3 radiance = envLookup(s, rayDir) * mk3(sThr[0][t], sThr[1][t], sThr[2][t]);
-                                float weight = (sFlags[t] & 2) ? 1.f : powerHeuristic(sExtPdf[t], environmentMapPdf(s, rayDir));
-                                v3 add = radiance * weight;
-                                sAccI[0][t] += add.x; sAccI[1][t] += add.y; sAccI[2][t] += add.z;
-                            }
-                            break;
-                        }
-                        nHits++;
-                        Surface isec;
-                        fetchSurface(s, hitPrim, hitBary, isec);
-                        Material material = texturedMaterial(s, isec);
-                        v3 throughput;
-                        if (k == 0) {
-                            material.baseColor = mk3(1.f);  // DENOISER_DEMODULATE (:175-178)
-                            if (material.type == Light) {   // :179-182
-                                sAccD[0][t] = sAccD[1][t] = sAccD[2][t] = 1.f;
-                                break;
-                            }
-                            throughput = mk3(1.f);
-                        } else {
-                            throughput = mk3(sThr[0][t], sThr[1][t], sThr[2][t]);
-                            if (material.type == Light) {  // :251-271
-                                if (dot(isec.norm, rayDir) < 0.f) break;
-                                v3 radiance = material.baseColor;
-                                bool deltaSample = (sFlags[t] & 2) != 0;
-                                v3 curPos = mk3(sCur[0][t], sCur[1][t], sCur[2][t]);
-                                float weight = deltaSample
-                                                   ? 1.f
-                                                   : powerHeuristic(sExtPdf[t],
-                                                                    pdfAreaToSolidAngle(luminance(radiance) * s.sumLightPowerInv *
-                                                                                            getPrimitiveArea(s, isec.primId),
-                                                                                        curPos, isec.pos, isec.norm));
-                                v3 add = radiance * throughput * weight;
-                                sAccI[0][t] += add.x; sAccI[1][t] += add.y; sAccI[2][t] += add.z;
-                                break;
-                            }
-                        }
-                        const int depth = k + 1;
-                        if (depth > maxDepth) break;  // loop bound of pathtrace.cu:187
-                        isec.wo = -rayDir;
-                        bool deltaBSDF = (material.type == Dielectric);
-                        if (material.type != Dielectric && dot(isec.norm, isec.wo) < 0.f) isec.norm = -isec.norm;
-                        Sampler rng{s.sobol, rngScramble, rngPtr};
-                        bool emitShadow = false;
-                        v3 shadowTarget = mk3(0.f);
-                        if (!deltaBSDF) {  // NEE (:195-208)
-                            v4 r4 = sample4D(rng);
-                            if (s.lightSamplerLength != 0) {
-                                LightPick lp = pickLightPoint(s, isec.pos, r4);
-                                v3 radiance = mk3(0.f), wi = mk3(0.f);
-                                float lightPdf = lightPdfUnoccluded(s, isec.pos, lp, radiance, wi);
-                                v3 cc = mk3(0.f);
-                                float nw = -1.f;
-                                if (lightPdf > 0.f) {
-                                    float BSDFPdf = materialPdf(material, isec.norm, isec.wo, wi);
-                                    cc = throughput * materialBSDF(material, isec.norm, isec.wo, wi) * radiance *
-                                         satDot(isec.norm, wi) / lightPdf * powerHeuristic(lightPdf, BSDFPdf);
-                                    nw = depth == 1 ? 0.f : 1.f;
-                                }
-                                sNee[0][t] = cc.x; sNee[1][t] = cc.y; sNee[2][t] = cc.z; sNee[3][t] = nw;
-                                shadowTarget = lp.sampled;
-                                emitShadow = true;  // traced even if nothing can be added
-                            }
-                        }
-                        sCur[0][t] = isec.pos.x; sCur[1][t] = isec.pos.y; sCur[2][t] = isec.pos.z;
-                        BSDFSample sample;
-                        sample.pdf = 0.f;
-                        materialSample(material, isec.norm, isec.wo, sample3D(rng), sample);
-                        rngScramble = rng.scramble;
-                        rngPtr = rng.ptr;
-                        int flags = 0;
-                        if (!(sample.type == Invalid) && !(sample.pdf < 1e-8f)) {
-                            bool deltaSample = (sample.type & Specular) != 0;
-                            throughput = throughput * (sample.bsdf / sample.pdf * (deltaSample ? 1.f : absDot(isec.norm, sample.dir)));
-                            Ray ray = makeOffsetedRay(isec.pos, sample.dir);
-                            sExtO[0][t] = ray.o.x; sExtO[1][t] = ray.o.y; sExtO[2][t] = ray.o.z;
-                            sExtD[0][t] = ray.d.x; sExtD[1][t] = ray.d.y; sExtD[2][t] = ray.d.z;
-                            sExtPdf[t] = sample.pdf;
-                            sThr[0][t] = throughput.x; sThr[1][t] = throughput.y; sThr[2][t] = throughput.z;
-                            flags = 1 | (deltaSample ? 2 : 0);
-                        }
-                        sFlags[t] = flags;
-                        k = depth;
-                        terminate = false;
-                        if (emitShadow) startShadow(isec.pos, shadowTarget);
+                    if (hitPrim != -1) nHits++;
+                    LanePath st{t, rngScramble, rngPtr};
+                    const PathStepResult r = pathStep(s, k, maxDepth, hitPrim, hitBary, rayD, st);
+                    if (r.goesOn()) {
+                        k++;
+                        if (!r.extension) sFlags[t] = 0;  // nothing is pending behind the shadow ray
+                        if (r.shadow) startShadow(r.shadowFrom, r.shadowTo);
                         else startExtensionOrFinish();
-                    } while (false);
-                    if (terminate) finishPixel();
+                    } else {
+                        finishPixel();
+                    }
                 }
             }
         }

@@ -5,7 +5,7 @@
 // pixel, 8x8 pixels per wave64) and are the "naive path tracer, no sort" of BASELINE config 2; the queue-based
 // pipeline is in kernels_wave.h and produces identical pixels.
 #pragma once
-#include "lights.h"
+#include "path_step.h"
 
 namespace rd {
 
@@ -173,9 +173,7 @@ __global__ __launch_bounds__(256) void k_path_trace_mega(DScene s, DCamera cam, 
                         if (!occ) lightPdf = lightPdfUnoccluded(s, isec.pos, lp, radiance, wi);
                     }
                     if (lightPdf > 0.f) {
-                        float BSDFPdf = materialPdf(material, isec.norm, isec.wo, wi);
-                        v3 c = throughput * materialBSDF(material, isec.norm, isec.wo, wi) * radiance *
-                               satDot(isec.norm, wi) / lightPdf * powerHeuristic(lightPdf, BSDFPdf);
+                        v3 c = neeContribution(material, isec, throughput, radiance, wi, lightPdf);
                         if (depth == 1) direct = direct + c;
                         else indirect = indirect + c;
                     }
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(256) void k_path_trace_mega(DScene s, DCamera cam, 
                 if (sample.type == Invalid) break;
                 else if (sample.pdf < 1e-8f) break;
                 bool deltaSample = (sample.type & Specular) != 0;
-                throughput = throughput * (sample.bsdf / sample.pdf * (deltaSample ? 1.f : absDot(isec.norm, sample.dir)));
+                throughput = throughput * bsdfSampleWeight(sample, isec.norm);
                 ray = makeOffsetedRay(isec.pos, sample.dir);
                 v3 curPos = isec.pos;
                 if (DUMP) dumpRay(dump, 0, ray.o, ray.d);
@@ -195,7 +193,7 @@ __global__ __launch_bounds__(256) void k_path_trace_mega(DScene s, DCamera cam, 
                 if (h.prim == -1) {  // :232-247
                     if (hasEnvMap(s)) {
                         v3 radiance = envLookup(s, ray.d) * throughput;
-                        float weight = deltaSample ? 1.f : powerHeuristic(sample.pdf, environmentMapPdf(s, ray.d));
+                        float weight = deltaSample ? 1.f : envMissWeight(s, ray.d, sample.pdf);
                         indirect = indirect + radiance * weight;
                     }
                     break;
@@ -207,23 +205,14 @@ __global__ __launch_bounds__(256) void k_path_trace_mega(DScene s, DCamera cam, 
                 if (material.type == Light) {
                     if (dot(isec.norm, ray.d) < 0.f) break;  // SCENE_LIGHT_SINGLE_SIDED (:252-256)
                     v3 radiance = material.baseColor;
-                    float weight = deltaSample
-                                       ? 1.f
-                                       : powerHeuristic(sample.pdf,
-                                                        pdfAreaToSolidAngle(luminance(radiance) * s.sumLightPowerInv *
-                                                                                getPrimitiveArea(s, isec.primId),
-                                                                            curPos, isec.pos, isec.norm));
+                    float weight = deltaSample ? 1.f : emitterHitWeight(s, radiance, isec, curPos, sample.pdf);
                     indirect = indirect + radiance * throughput * weight;
                     break;
                 }
             }
         } while (false);
-        if (hasNanOrInf(direct)) direct = mk3(0.f);
-        if (hasNanOrInf(indirect)) indirect = mk3(0.f);
-        direct = HDRToLDR(direct);
-        indirect = HDRToLDR(indirect);
-        storeRunningMean(directIllum, px.out, direct, iter);
-        storeRunningMean(indirectIllum, px.out, indirect, iter);
+        storeRunningMean(directIllum, px.out, finishSample(direct), iter);
+        storeRunningMean(indirectIllum, px.out, finishSample(indirect), iter);
     }
     if (COUNT) flushCounters(s.counters, nClosest, nAny, nHits, ws);
 }

@@ -91,11 +91,7 @@ __global__ __launch_bounds__(64) void k_walk_persistent(DScene s, const float *_
                         const v3 b = mk3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
                         Ray ray;
                         if (ANY) {  // testOcclusion(a, b) (scene.h:303-315)
-                            v3 dir = b - a;
-                            float dist = length(dir);
-                            dir = dir / dist;
-                            ray = makeOffsetedRay(a, dir);
-                            tmax = dist - 1e-4f;
+                            ray = shadowRay(a, b, tmax);
                         } else {
                             ray = Ray{a, b};
                             tmax = 3.402823466e+38f;
@@ -337,11 +333,7 @@ __global__ __launch_bounds__(64, COUNT ? 1 : 7) void k_walk_pair(DScene s, const
                         const v3 b = mk3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
                         Ray ray;
                         if (ANY) {  // testOcclusion(a, b) (scene.h:303-315)
-                            v3 dir = b - a;
-                            float dist = length(dir);
-                            dir = dir / dist;
-                            ray = makeOffsetedRay(a, dir);
-                            tmax = dist - 1e-4f;
+                            ray = shadowRay(a, b, tmax);
                         } else {
                             ray = Ray{a, b};
                             tmax = 3.402823466e+38f;
@@ -465,11 +457,7 @@ __global__ __launch_bounds__(kWgTraceThreads) void k_trace_wg(DScene s, const fl
         Ray ray;
         float tmax;
         if (ANY) {  // testOcclusion(a, b) (scene.h:303-315)
-            v3 dir = b - a;
-            float dist = length(dir);
-            dir = dir / dist;
-            ray = makeOffsetedRay(a, dir);
-            tmax = dist - 1e-4f;
+            ray = shadowRay(a, b, tmax);
         } else {
             ray = Ray{a, b};
             tmax = 3.402823466e+38f;
@@ -509,11 +497,7 @@ __global__ __launch_bounds__(kWgTraceThreads) void k_trace_wg_list(DScene s, con
         Ray ray;
         float tmax;
         if (ANY) {
-            v3 dir = b - a;
-            float dist = length(dir);
-            dir = dir / dist;
-            ray = makeOffsetedRay(a, dir);
-            tmax = dist - 1e-4f;
+            ray = shadowRay(a, b, tmax);
         } else {
             ray = Ray{a, b};
             tmax = 3.402823466e+38f;

@@ -6,7 +6,8 @@
 //   * each path owns its accumulators (no cross-path atomics), and launches are stream-ordered so that the
 //     additions to `direct`/`indirect` happen in the megakernel's order (NEE of bounce d, then the emitter hit
 //     of bounce d);
-//   * all arithmetic is the same device functions the megakernel calls.
+//   * all arithmetic is the same device functions the megakernel calls: the bounce body is pathStep (path_step.h), built from the
+//     four expressions k_path_trace_mega calls in place, and every shadow ray is shadowRay's (traverse.h).
 //
 // Launch structure per frame (maxDepth = D):  memset(counters) · raygen · for k = 0..D { trace(k) · shade(k) } · finish
 // (optionally as three sub-frames on three streams, see k_wf_raygen; the material sort happens inside shade, see k_wf_shade)
@@ -64,6 +65,41 @@ struct WaveWorkspace {
     int *treeOvf;     // k_wf_trace<.., true>: its lanes' stacks beyond their LDS rings, [logical wave][treeOvfDepth][64] int2 (traverse.h, pairPush)
     int treeOvfDepth;
     WaveCounters *ctr;
+};
+
+// The ray trace(k) walks for path slot p, and how far: the shadow ray of the slot's pending NEE sample (prevPos -> sht), or its
+// extension ray as shade(k-1) / raygen stored it.  k_wf_trace builds every ray here, so the workgroup's first list and the lane
+// that meets the same entry classify one and the same ray.
+RD_DEV Ray wfSlotRay(const WaveWorkspace &w, int p, bool shadow, float &limit) {
+    if (shadow) {
+        const float4 x = w.prevPos[p], y = w.sht[p];
+        return shadowRay(mk3(x.x, x.y, x.z), mk3(y.x, y.y, y.z), limit);
+    }
+    const float4 o = w.ro[p], d = w.rd[p];
+    limit = 3.402823466e+38f;
+    return Ray{mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z)};
+}
+
+// Path slot p as pathStep sees it (path_step.h): every getter is a load from the slot's record, every setter a store to it.
+struct WaveSlotPath {
+    const WaveWorkspace &w;
+    const int p;
+    const bool delta;  // rd[p].w, which the caller has loaded with the ray's direction
+    RD_DEV v3 throughput() const { const float4 t = w.thr[p]; return mk3(t.x, t.y, t.z); }
+    RD_DEV float samplePdf() const { return w.ro[p].w; }
+    RD_DEV bool sampleDelta() const { return delta; }
+    RD_DEV v3 prevPos() const { const float4 c = w.prevPos[p]; return mk3(c.x, c.y, c.z); }
+    RD_DEV void setDirect(v3 v) { w.accD[p] = make_float4(v.x, v.y, v.z, 0.f); }
+    RD_DEV void addIndirect(v3 v) { const float4 a = w.accI[p]; w.accI[p] = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, 0.f); }
+    RD_DEV Sampler rng(const DScene &s) const { const uint2 r = w.rng[p]; return Sampler{s.sobol, r.x, (int)r.y}; }
+    RD_DEV void setNee(v3 c, float nw) { w.nee[p] = make_float4(c.x, c.y, c.z, nw); }
+    RD_DEV void setPrevPos(v3 x) { w.prevPos[p] = make_float4(x.x, x.y, x.z, 0.f); }
+    RD_DEV void setRay(const Ray &ray, float pdf, bool deltaSample, v3 throughput, const Sampler &rng) {
+        w.ro[p] = make_float4(ray.o.x, ray.o.y, ray.o.z, pdf);
+        w.rd[p] = make_float4(ray.d.x, ray.d.y, ray.d.z, deltaSample ? 1.f : 0.f);
+        w.thr[p] = make_float4(throughput.x, throughput.y, throughput.z, 0.f);
+        w.rng[p] = make_uint2(rng.scramble, (unsigned)rng.ptr);
+    }
 };
 
 
@@ -209,7 +245,7 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
 // six threaded arrays — same triangle tests in the same order, same counters.  Chosen by the host for big scenes (radish_hip.hip,
 // usePairs): a sixth of the node footprint and half the dependent round trips (profiles/r03_h_*).
 #ifndef RD_WF_TRACE_WAVES  // waves per SIMD the threaded variant is held to: its occupancy step (72 VGPRs).  Unbounded, the entry
-#define RD_WF_TRACE_WAVES 7  // barrier of workgroupTicket makes the allocator take 73 (6 waves); held to 7 it takes 70, no scratch
+#define RD_WF_TRACE_WAVES 7  // barrier of workgroupTicket makes the allocator take 73 (6 waves); held to 7 it takes 69, no scratch
 #endif
 #ifndef RD_WF_PAIR_WAVES
 #define RD_WF_PAIR_WAVES 1  // waves per SIMD the pair variant is held to (1: whatever its registers allow)
@@ -270,21 +306,8 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
         const int e = w.litq[k & 1][it];
         const bool sh = (e & kWfLitShadow) != 0;
         const int pp = e & (kWfLitShadow - 1);
-        Ray ray;
         float lim;
-        if (sh) {
-            const float4 x4 = w.prevPos[pp], y4 = w.sht[pp];
-            const v3 x = mk3(x4.x, x4.y, x4.z), y = mk3(y4.x, y4.y, y4.z);
-            v3 dir = y - x;  // DevScene::testOcclusion's ray set-up (scene.h:304-311)
-            const float dist = length(dir);
-            dir = dir / dist;
-            lim = dist - 1e-4f;
-            ray = makeOffsetedRay(x, dir);
-        } else {
-            const float4 o = w.ro[pp], d = w.rd[pp];
-            ray = Ray{mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z)};
-            lim = 3.402823466e+38f;
-        }
+        const Ray ray = wfSlotRay(w, pp, sh, lim);
         const RaySlab urs = makeRaySlab(ray);
         if (urs.cls == 0 || end == 0) continue;  // the hint did not hold: a lane takes this entry below
         const NodeRec *un = s.nodes[getMTBVHId(-ray.d)];
@@ -358,25 +381,10 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
             }
         }
         if (doStart) {
-            Ray ray;
-            if (isShadow) {
-                float4 x4 = w.prevPos[p], y4 = w.sht[p];
-                v3 x = mk3(x4.x, x4.y, x4.z), y = mk3(y4.x, y4.y, y4.z);
-                v3 dir = y - x;  // DevScene::testOcclusion's ray set-up (scene.h:304-311)
-                float dist = length(dir);
-                dir = dir / dist;
-                tmax = dist - 1e-4f;
-                ray = makeOffsetedRay(x, dir);
-                nAny++;
-            } else if (p >= 0) {
-                float4 o = w.ro[p], d = w.rd[p];
-                ray = Ray{mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z)};
-                tmax = 3.402823466e+38f;
-                nClosest++;
-            } else {
-                ray = Ray{mk3(0.f), mk3(0.f, 0.f, 1.f)};  // off-frame slot of bounce 0: nothing to trace
-            }
-            if (p >= 0) {
+            if (p >= 0) {  // else: an off-frame slot of bounce 0, nothing to trace
+                const Ray ray = wfSlotRay(w, p, isShadow, tmax);
+                if (isShadow) nAny++;
+                else nClosest++;
                 rs = makeRaySlab(ray);
                 pending = -1;
                 if (PAIRS) {
@@ -550,7 +558,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
 constexpr int kSortChunks = 16;                  // chunks of 64 records per sorted packet
 constexpr int kSortPacket = 64 * kSortChunks;    // records a wave bins at a time
 #ifndef RD_WF_SHADE_WAVES
-#define RD_WF_SHADE_WAVES 1  // waves per SIMD k_wf_shade is held to (1: whatever its 155 VGPRs allow = 3)
+#define RD_WF_SHADE_WAVES 1  // waves per SIMD k_wf_shade is held to (1: whatever its 147 VGPRs allow = 3)
 #endif
 __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, WaveWorkspace w, int k, int maxDepth, int sorted) {
     __shared__ int sSorted[4][kSortPacket];  // per wave of the workgroup: the packet's path slots in class order
@@ -628,100 +636,23 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
                 active = p >= 0;
             }
             if (active) {
-                int4 h = w.hit[p];
-                float4 rdw = w.rd[p];
-                v3 rayDir = mk3(rdw.x, rdw.y, rdw.z);
-                do {
-                    if (h.x == -1) {  // miss: primary → direct = 1 (pathtrace.cu:169-172); later → env map (:232-247)
-                        if (k == 0) {
-                            w.accD[p] = make_float4(1.f, 1.f, 1.f, 0.f);
-                        } else if (hasEnvMap(s)) {
-                            float4 t = w.thr[p], o = w.ro[p];
-                            v3 radiance = envLookup(s, rayDir) * mk3(t.x, t.y, t.z);
-                            float weight = (rdw.w != 0.f) ? 1.f : powerHeuristic(o.w, environmentMapPdf(s, rayDir));
-                            v3 add = radiance * weight;
-                            float4 a = w.accI[p];
-                            w.accI[p] = make_float4(a.x + add.x, a.y + add.y, a.z + add.z, 0.f);
-                        }
-                        break;
-                    }
-                    Surface isec;
-                    fetchSurface(s, h.x, mk2(__int_as_float(h.y), __int_as_float(h.z)), isec);
-                    Material material = texturedMaterial(s, isec);
-                    v3 throughput;
-                    if (k == 0) {
-                        material.baseColor = mk3(1.f);  // DENOISER_DEMODULATE (:175-178)
-                        if (material.type == Light) {   // :179-182
-                            w.accD[p] = make_float4(1.f, 1.f, 1.f, 0.f);
-                            break;
-                        }
-                        throughput = mk3(1.f);
-                    } else {
-                        float4 t = w.thr[p];
-                        throughput = mk3(t.x, t.y, t.z);
-                        if (material.type == Light) {  // :251-271
-                            if (dot(isec.norm, rayDir) < 0.f) break;
-                            v3 radiance = material.baseColor;
-                            float4 o = w.ro[p], cp = w.prevPos[p];
-                            bool deltaSample = rdw.w != 0.f;
-                            float weight = deltaSample
-                                               ? 1.f
-                                               : powerHeuristic(o.w, pdfAreaToSolidAngle(luminance(radiance) * s.sumLightPowerInv *
-                                                                                            getPrimitiveArea(s, isec.primId),
-                                                                                        mk3(cp.x, cp.y, cp.z), isec.pos, isec.norm));
-                            v3 add = radiance * throughput * weight;
-                            float4 a = w.accI[p];
-                            w.accI[p] = make_float4(a.x + add.x, a.y + add.y, a.z + add.z, 0.f);
-                            break;
-                        }
-                    }
-                    const int depth = k + 1;
-                    if (depth > maxDepth) break;  // loop bound of pathtrace.cu:187
-                    isec.wo = -rayDir;
-                    bool deltaBSDF = (material.type == Dielectric);
-                    if (material.type != Dielectric && dot(isec.norm, isec.wo) < 0.f) isec.norm = -isec.norm;
-                    uint2 rs = w.rng[p];
-                    Sampler rng{s.sobol, rs.x, (int)rs.y};
-                    if (!deltaBSDF) {  // NEE (:195-208); the shadow ray itself is traced by trace(k+1)
-                        v4 r4 = sample4D(rng);
-                        if (s.lightSamplerLength != 0) {
-                            LightPick lp = pickLightPoint(s, isec.pos, r4);
-                            v3 radiance = mk3(0.f), wi = mk3(0.f);
-                            float lightPdf = lightPdfUnoccluded(s, isec.pos, lp, radiance, wi);
-                            float4 n = make_float4(0.f, 0.f, 0.f, -1.f);
-                            if (lightPdf > 0.f) {
-                                float BSDFPdf = materialPdf(material, isec.norm, isec.wo, wi);
-                                v3 cc = throughput * materialBSDF(material, isec.norm, isec.wo, wi) * radiance *
-                                        satDot(isec.norm, wi) / lightPdf * powerHeuristic(lightPdf, BSDFPdf);
-                                n = make_float4(cc.x, cc.y, cc.z, depth == 1 ? 0.f : 1.f);
-                            }
-                            w.nee[p] = n;
-                            w.sht[p] = make_float4(lp.sampled.x, lp.sampled.y, lp.sampled.z, 0.f);
-                            emitShadow = true;  // traced even when nothing can be added: sampleDirectLight tests
-                                                // occlusion before the single-sided rejection
-                            {  // a hint only (trace classifies the ray it builds): some component below 1.1e-6 of the length
-                                const v3 dl = lp.sampled - isec.pos;
-                                const float l2 = dot(dl, dl) * 1.21e-12f;
-                                litShadow = dl.x * dl.x < l2 || dl.y * dl.y < l2 || dl.z * dl.z < l2;
-                            }
-                        }
-                    }
-                    w.prevPos[p] = make_float4(isec.pos.x, isec.pos.y, isec.pos.z, 0.f);
-                    BSDFSample sample;
-                    sample.pdf = 0.f;
-                    materialSample(material, isec.norm, isec.wo, sample3D(rng), sample);
-                    if (sample.type == Invalid) break;
-                    else if (sample.pdf < 1e-8f) break;
-                    bool deltaSample = (sample.type & Specular) != 0;
-                    throughput = throughput * (sample.bsdf / sample.pdf * (deltaSample ? 1.f : absDot(isec.norm, sample.dir)));
-                    Ray ray = makeOffsetedRay(isec.pos, sample.dir);
-                    w.ro[p] = make_float4(ray.o.x, ray.o.y, ray.o.z, sample.pdf);
-                    w.rd[p] = make_float4(ray.d.x, ray.d.y, ray.d.z, deltaSample ? 1.f : 0.f);
-                    w.thr[p] = make_float4(throughput.x, throughput.y, throughput.z, 0.f);
-                    w.rng[p] = make_uint2(rng.scramble, (unsigned)rng.ptr);
+                const int4 h = w.hit[p];
+                const float4 rdw = w.rd[p];
+                WaveSlotPath st{w, p, rdw.w != 0.f};
+                const PathStepResult r = pathStep(s, k, maxDepth, h.x, mk2(__int_as_float(h.y), __int_as_float(h.z)), mk3(rdw.x, rdw.y, rdw.z), st);
+                // the rays go to trace(k+1)'s queues below.  The two hints (trace classifies the ray it builds): some component of the
+                // direction below 1.1e-6 of its length
+                if (r.shadow) {
+                    w.sht[p] = make_float4(r.shadowTo.x, r.shadowTo.y, r.shadowTo.z, 0.f);
+                    emitShadow = true;
+                    const v3 dl = r.shadowTo - r.shadowFrom;
+                    const float l2 = dot(dl, dl) * 1.21e-12f;
+                    litShadow = dl.x * dl.x < l2 || dl.y * dl.y < l2 || dl.z * dl.z < l2;
+                }
+                if (r.extension) {
                     emitRay = true;
-                    litRay = fabs_(ray.d.x) < 1.1e-6f || fabs_(ray.d.y) < 1.1e-6f || fabs_(ray.d.z) < 1.1e-6f;
-                } while (false);
+                    litRay = fabs_(r.ray.d.x) < 1.1e-6f || fabs_(r.ray.d.y) < 1.1e-6f || fabs_(r.ray.d.z) < 1.1e-6f;
+                }
             }
             if (__ballot(litShadow || litRay) != 0ull) {  // rare: a few hundred rays per stage
                 int *lq = w.litq[(k + 1) & 1];
@@ -766,9 +697,7 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
 // One thread per pixel.  The pixel's `samples` slots (k_wf_raygen's order) are folded into its two running
 // means in sample order, each with storeRunningMean's expression at its own iter, so the image equals `samples` single launches.
 RD_DEV v3 foldRunningMean(v3 mean, float4 acc, int iter) {
-    v3 v = mk3(acc.x, acc.y, acc.z);
-    if (hasNanOrInf(v)) v = mk3(0.f);
-    return (mean * float(iter) + HDRToLDR(v)) / float(iter + 1);
+    return (mean * float(iter) + finishSample(mk3(acc.x, acc.y, acc.z))) / float(iter + 1);
 }
 __global__ __launch_bounds__(256) void k_wf_finish(PixelMap pm, WaveWorkspace w, int iter, int samples, float *__restrict__ directIllum,
                                                    float *__restrict__ indirectIllum, int part, int parts) {

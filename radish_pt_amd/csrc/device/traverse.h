@@ -591,17 +591,23 @@ RD_DEV HitRec traceClosest(const DScene &s, const Ray &ray, WalkStats &ws, bool 
     return h;
 }
 
-// DevScene::testOcclusion (scene.h:303-334)
-template <bool COUNT>
-RD_DEV bool traceOccluded(const DScene &s, v3 x, v3 y, WalkStats &ws, bool active = true) {
-    const float eps = 1e-4f;
+// DevScene::testOcclusion's ray set-up (scene.h:303-315): the ray from x towards y and how far along it a hit occludes.  Every kernel
+// that traces a shadow ray builds it here.
+RD_DEV Ray shadowRay(v3 x, v3 y, float &limit) {
     v3 dir = y - x;
     float dist = length(dir);
     dir = dir / dist;
-    dist -= eps;
-    Ray ray = makeOffsetedRay(x, dir);
+    limit = dist - 1e-4f;
+    return makeOffsetedRay(x, dir);
+}
+
+// DevScene::testOcclusion (scene.h:303-334)
+template <bool COUNT>
+RD_DEV bool traceOccluded(const DScene &s, v3 x, v3 y, WalkStats &ws, bool active = true) {
+    float limit;
+    Ray ray = shadowRay(x, y, limit);
     HitRec h;
-    return walkRay<COUNT, true>(s, ray, dist, h, ws, active);
+    return walkRay<COUNT, true>(s, ray, limit, h, ws, active);
 }
 
 // ---- walks over SIBLING PAIRS (DScene::pairs, layouts.h) -----------------------------------------------------------------------
