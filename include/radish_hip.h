@@ -542,6 +542,12 @@ int rdh_debug_persist_stamps(rdh_ctx *ctx, uint64_t *out5x4096);
  * wave-steps, [9] box lane-steps, [10] leaf calls, [11] leaf lanes, [12] shade calls, [13] shade lanes, [14] raygen calls,
  * [15] raygen lanes.  RDH_ERR_UNSUPPORTED otherwise. */
 int rdh_debug_persist_phases(rdh_ctx *ctx, uint64_t *out16);
+/* Diagnostic builds only (-DRD_WF_STAMPS): wall-clock stamps (100 MHz ticks) of the trace stages of the last wavefront pass
+ * (its first pipeline), out[(stage * waves + logical wave) * 3 + i] — i = 0 the wave entered k_wf_trace, 1 it first found the
+ * stage's queue exhausted, 2 it left; 0 where a wave wrote none.  *stages and *waves are always set; the stamps are copied when
+ * capacity (in uint64_t) holds stages * waves * 3 of them, so a first call with capacity 0 sizes the second.  Blocking.
+ * RDH_ERR_UNSUPPORTED otherwise. */
+int rdh_debug_wf_stamps(rdh_ctx *ctx, uint64_t *out, int64_t capacity, int32_t *stages, int32_t *waves);
 
 /* Time of the most recent render call's kernels, measured with hipEvents on the context's stream (blocking);
  * the reference prints this figure from pathTrace (src/pathtrace.cu:364-374). */

@@ -61,7 +61,7 @@ EXPORTS = [
     "rdh_path_trace_direct", "rdh_gbuffer_render", "rdh_restir_init", "rdh_restir_free", "rdh_restir_direct",
     "rdh_restir_read", "rdh_restir_read_scratch", "rdh_copy_image_to_pbo", "rdh_denoise_eaw", "rdh_denoise_svgf", "rdh_denoise_modulate",
     "rdh_denoise_add", "rdh_denoise_temporal_accumulate", "rdh_denoise_estimate_variance", "rdh_denoise_filter_variance", "rdh_restir_exchange_pack", "rdh_restir_exchange_unpack", "rdh_trace_closest", "rdh_trace_occluded", "rdh_counters_reset", "rdh_counters_read",
-    "rdh_last_kernel_ms", "rdh_profile_reset", "rdh_profile_read", "rdh_debug_persist_stamps", "rdh_debug_persist_phases",
+    "rdh_last_kernel_ms", "rdh_profile_reset", "rdh_profile_read", "rdh_debug_persist_stamps", "rdh_debug_persist_phases", "rdh_debug_wf_stamps",
     "rdh_gbuffer_exchange_pack", "rdh_gbuffer_exchange_unpack", "rdh_comm_unique_id", "rdh_comm_init", "rdh_comm_destroy",
     "rdh_dump_rays", "rdh_set_occupancy_share", "rdh_allgather_tiles", "rdh_path_trace_gathered", "rdh_restir_exchange", "rdh_restir_direct_gathered", "rdh_gbuffer_exchange",
     "rdh_comm_init_all", "rdh_path_trace_gathered_all", "rdh_gbuffer_exchange_all", "rdh_restir_direct_gathered_all",
@@ -870,6 +870,17 @@ class Context:
     def debug_persist_stamps(self):
         out = np.zeros((5, 4096), dtype=np.uint64)
         self.check(lib().rdh_debug_persist_stamps(self.h, out.ctypes.data))
+        return out
+
+    def debug_wf_stamps(self):
+        """uint64 [stages, waves, 3] (entry, queue dry, exit; 100 MHz ticks) of the last wavefront pass's trace stages: a
+        -DRD_WF_STAMPS build via RADISH_HIP_LIB.  (Bound here, not in lib(): RADISH_HIP_LIB may name a build from before this entry.)"""
+        fn = lib().rdh_debug_wf_stamps
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int32
+        stages, waves = C.c_int32(0), C.c_int32(0)
+        self.check(fn(self.h, None, 0, C.byref(stages), C.byref(waves)))
+        out = np.zeros((stages.value, waves.value, 3), dtype=np.uint64)
+        self.check(fn(self.h, out.ctypes.data, out.size, C.byref(stages), C.byref(waves)))
         return out
 
     def debug_persist_phases(self):

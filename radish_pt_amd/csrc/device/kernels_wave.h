@@ -11,7 +11,8 @@
 //
 // Launch structure per frame (maxDepth = D):  memset(counters) · raygen · for k = 0..D { trace(k) · shade(k) } · finish
 // (optionally as three sub-frames on three streams, see k_wf_raygen; the material sort happens inside shade, see k_wf_shade)
-//   trace(k)  = any-hit for the shadow rays emitted by shade(k-1)  +  closest-hit for the rays of bounce k
+//   trace(k)  = closest-hit for the rays of bounce k, then any-hit for the shadow rays emitted by shade(k-1): one queue of work
+//               items, the (long) extension rays handed out first so that the stage ends on the (short) shadow rays
 //   shade(k)  = surface fetch for hit k, emitter/miss termination, then bounce body k+1 (NEE sample → shadow
 //               queue, BSDF sample → next ray queue) with wave64 ballot compaction
 // trace and shade are persistent kernels: a fixed grid of waves pulls 64-item packets from device-side queue
@@ -64,6 +65,10 @@ struct WaveWorkspace {
     int litCap;       // entries a stage may hold: min(kWfLitCap, 64 * waves of the trace grid)
     int *treeOvf;     // k_wf_trace<.., true>: its lanes' stacks beyond their LDS rings, [logical wave][treeOvfDepth][64] int2 (traverse.h, pairPush)
     int treeOvfDepth;
+#ifdef RD_WF_STAMPS  // diagnostic build only: k_wf_trace's per-wave wall-clock stamps, [stage][logical wave][kWfStampKinds]; null: none
+    unsigned long long *stamps;
+    int stampWaves;   // logical waves of the trace grid
+#endif
     WaveCounters *ctr;
 };
 
@@ -225,7 +230,7 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
     if (blockIdx.x == 0 && threadIdx.x == 0) w.ctr->rayCount[0].v = int(nGroups) * 64;
 }
 
-// ---- trace(k): shadow rays of bounce k (from shade(k-1)) + closest hits of bounce k ---------------------------
+// ---- trace(k): closest hits of bounce k + shadow rays of bounce k (from shade(k-1)) ---------------------------
 // Persistent waves with LANE REFILL: a wave reserves 64 consecutive work items per atomic and hands them to lanes
 // one by one as their previous ray finishes, so a wave never idles behind its longest ray (rays of one packet differ
 // several-fold in visit count after the first bounce).  Shadow (any-hit) and extension (closest-hit) rays run through
@@ -235,6 +240,28 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
 #endif
 #ifndef RD_WF_FINISH_MIN  // retire finished rays once they are this many 64ths of the wave's busy lanes (0: every iteration).  With
 #define RD_WF_FINISH_MIN 16  // three sub-frames, teapots / Cornell: 0 -> 9.31 / 4.02 ms, 8 -> 9.20 / 3.99, 16 -> 9.05 / 3.93, 24 -> 9.08 / 3.98
+#endif
+// The order of a stage's work items: [0, nRay) are the extension rays of bounce k (rayq), [nRay, nRay + nShadow) the shadow rays that
+// shade(k-1) emitted (shadowq), and both the static first packets and the shared head hand items out in increasing order.  A shadow
+// ray ends at its first accepted triangle within its segment; an extension ray walks to its closest hit, several times as far.  With
+// the shadow rays first (the order until DESIGN 5b, "Extension rays first") every stage ended on its longest rays with nothing left to
+// refill the lanes they leave idle.  Nothing reads an order: a shadow ray adds to accD / accI of its own slot, an extension ray writes
+// hit of its own.  1: the old order (measurements).  Teapots 1080p, 8 bounces, sorted, one pipeline, 1 / 0: 8.41 / 7.94 ms per frame,
+// stages 1-8 of this kernel 6.31 / 5.80 ms; config 5's scene at 4K 33.04 / 32.59 ms (profiles/wf_order/)
+#ifndef RD_WF_SHADOW_FIRST
+#define RD_WF_SHADOW_FIRST 0
+#endif
+// RD_WF_STAMPS (diagnostic build only, like RD_PERSIST_STAMPS): lane 0 of every wave stores wall_clock64() (100 MHz) into its own
+// slot of WaveWorkspace::stamps when it enters the kernel, when it first finds the stage's queue exhausted, and when it leaves —
+// plain stores, no shared counter.  The entry stamp is the reference the other two are read against (the earliest one of a stage is
+// the launch's start: scripts/wf_stage_tails.py).  The default build holds none of it.
+constexpr int kWfStampKinds = 3;  // entry, queue dry, exit
+#ifdef RD_WF_STAMPS
+#define RD_WF_STAMP(kind) do { if (stampAt && (threadIdx.x & 63u) == 0u) stampAt[kind] = wall_clock64(); } while (0)
+#define RD_WF_STAMP_DRY() do { if (exhausted && !stampedDry) { stampedDry = true; RD_WF_STAMP(1); } } while (0)
+#else
+#define RD_WF_STAMP(kind) ((void)0)
+#define RD_WF_STAMP_DRY() ((void)0)
 #endif
 #ifndef RD_WF_COOP_LONE  // a lone walking lane is walked by the whole wave (coopWalk): 0.5-1 % on either scene
 #define RD_WF_COOP_LONE 1
@@ -254,6 +281,11 @@ template <bool COUNT, bool PAIRS = false>
 __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ? RD_WF_TRACE_WAVES : 1)) void k_wf_trace(DScene s, WaveWorkspace w, int k) {
     WaveCounters *c = w.ctr;
     const int wg = workgroupTicket(c->traceTicket[k]);  // stands for blockIdx.x below (see wavePull)
+#ifdef RD_WF_STAMPS
+    unsigned long long *const stampAt = w.stamps ? w.stamps + ((size_t)k * (size_t)w.stampWaves + (size_t)logicalWave(wg)) * kWfStampKinds : nullptr;
+    bool stampedDry = false;
+    RD_WF_STAMP(0);
+#endif
     const int nShadow = (k > 0) ? c->shadowCount[k - 1].v : 0;
     const int nRay = c->rayCount[k].v;
     const int total = nShadow + nRay;
@@ -267,6 +299,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
     int resNext = logicalWave(wg) * kPacket, resEnd = resNext + kPacket;
     bool exhausted = resNext >= total;
     if (resEnd > total) resEnd = total;
+    RD_WF_STAMP_DRY();
 
     // per-lane walker state
     bool alive = false;
@@ -373,13 +406,19 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
                 if (!alive && !doStart && p < 0 && myRank >= taken && myRank < taken + give) {
                     const int item = resNext + (myRank - taken);
                     doStart = true;
+#if RD_WF_SHADOW_FIRST
                     isShadow = item < nShadow;
                     p = isShadow ? w.shadowq[item] : rayq[item - nShadow];
+#else
+                    isShadow = item >= nRay;
+                    p = isShadow ? w.shadowq[item - nRay] : rayq[item];
+#endif
                 }
                 resNext += give;
                 taken += give;
             }
         }
+        RD_WF_STAMP_DRY();
         if (doStart) {
             if (p >= 0) {  // else: an off-frame slot of bounce 0, nothing to trace
                 const Ray ray = wfSlotRay(w, p, isShadow, tmax);
@@ -544,6 +583,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
             p = -1;
         }
     }
+    RD_WF_STAMP(2);
     if (COUNT) flushCounters(s.counters, nClosest, nAny, nHits, ws);
 }
 

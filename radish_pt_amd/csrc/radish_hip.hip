@@ -237,6 +237,10 @@ struct rdh_ctx {
     long long wfCapacity = 0;   // path slots each workspace holds
     std::vector<void *> wfAllocs;
     hipEvent_t evWfFork = nullptr, evWfJoin = nullptr;
+#ifdef RD_WF_STAMPS
+    GrowBuf wfStamps{bufs};  // stamps (unsigned long long): k_wf_trace's, of the last wavefront pass (rdh_debug_wf_stamps)
+    int wfStampStages = 0, wfStampWaves = 0;
+#endif
 
     // device BVH builder (kernels_bvh.h) and rdh_scene_update_geometry
     GrowBuf bvhScratch{bufs};        // primitives: the BvhWork buffers, one allocation
@@ -832,6 +836,19 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
             c->wf[h].treeOvfDepth = ovfDepth;
         }
     }
+#ifdef RD_WF_STAMPS  // pipeline 0's trace stages stamp their waves (kernels_wave.h, RD_WF_STAMP); the others get no buffer
+    {
+        const size_t stamps = (size_t)(maxDepth + 1) * traceGrid * 4 * kWfStampKinds;
+        if (int rc = grow(c, c->wfStamps, stamps, stamps * sizeof(unsigned long long), Busy::Device)) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->wfStamps.p, 0, stamps * sizeof(unsigned long long), c->stream));
+        for (int h = 0; h < kWfParts; h++) {
+            c->wf[h].stamps = h == 0 ? c->wfStamps.as<unsigned long long>() : nullptr;
+            c->wf[h].stampWaves = (int)(traceGrid * 4);
+        }
+        c->wfStampStages = maxDepth + 1;
+        c->wfStampWaves = (int)(traceGrid * 4);
+    }
+#endif
     // RDH_PT_PROFILE with sub-frames: the pipelines' launches overlap by design, so what is timed is the FRAME — one event pair
     // from before the fork to after the join, on the context's stream (one pipeline: a pair around every k_wf_trace launch)
     const long pf = parts >= 2 ? profBegin(c, flags) : -1;
@@ -2373,6 +2390,20 @@ int rdh_debug_persist_stamps(rdh_ctx *c, uint64_t *out5x4096) {
     return RDH_OK;
 #else
     return fail(c, RDH_ERR_UNSUPPORTED, "library built without RD_PERSIST_STAMPS");
+#endif
+}
+
+int rdh_debug_wf_stamps(rdh_ctx *c, uint64_t *out, int64_t capacity, int32_t *stages, int32_t *waves) {
+    if (!c || !stages || !waves || capacity < 0 || (capacity > 0 && !out)) return RDH_ERR_ARGS;
+#ifdef RD_WF_STAMPS
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *stages = c->wfStampStages;
+    *waves = c->wfStampWaves;
+    const int64_t n = (int64_t)c->wfStampStages * c->wfStampWaves * kWfStampKinds;
+    if (n > 0 && capacity >= n) HIP_TRY(c, hipMemcpy(out, c->wfStamps.p, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost));
+    return RDH_OK;
+#else
+    return fail(c, RDH_ERR_UNSUPPORTED, "library built without RD_WF_STAMPS");
 #endif
 }
 
