@@ -48,17 +48,25 @@ struct WaveCounters {
     WaveCounter shadeTicket[kMaxWaveDepth + 2][kTicketShards];
 };
 
+// Slots.  A path's HOME slot is its position in bounce 0's identity queue (k_wf_raygen); its two accumulators stay there for the whole
+// frame, and k_wf_finish maps it to the pixel.  Everything else that rides with the path is rewritten by every bounce (pathStep's
+// setters), so shade(k) writes it to a FRESH slot: the record's position q in stage k's processing order (k_wf_shade), unique and below
+// rayCount[k].  Stage k + 1 then works in a slot space of rayCount[k] entries that are dense but for the paths that died in bounce
+// k, instead of survivors scattered over the whole frame's slots: its loads and stores touch the lines of the live paths only.  The
+// riding state is two sets: stage k (trace(k), shade(k)) reads set k & 1, shade(k) writes set (k + 1) & 1, k_wf_raygen writes set 0,
+// so nothing is written to the set a stage reads.  `hit` is single: trace(k) writes it and shade(k) reads it in the same slot space.
+// Home rides in thr.w and, beside the kind, in nee.w (wfNeeTag): where it is needed it has been loaded anyway.
 struct WaveWorkspace {
-    float4 *ro;       // ray origin.xyz (offset applied), w = pdf of the BSDF sample that made this ray
-    float4 *rd;       // ray direction.xyz, w = 1 if that sample was specular (deltaSample)
-    float4 *thr;      // throughput.xyz
-    float4 *prevPos;  // position the ray left from (curPos, pathtrace.cu:227) = origin of the pending shadow ray
-    float4 *accD;     // direct.xyz
-    float4 *accI;     // indirect.xyz
-    float4 *nee;      // pending NEE contribution.xyz, w: 0 → direct, 1 → indirect, -1 → nothing to add
-    float4 *sht;      // shadow-ray target.xyz
-    uint2 *rng;       // {scramble, ptr}
-    int4 *hit;        // {primId, bary.x, bary.y, shading class of the hit's material}
+    float4 *ro[2];       // ray origin.xyz (offset applied), w = pdf of the BSDF sample that made this ray
+    float4 *rd[2];       // ray direction.xyz, w = 1 if that sample was specular (deltaSample)
+    float4 *thr[2];      // throughput.xyz, w = the bits of the home slot
+    float4 *prevPos[2];  // position the ray left from (curPos, pathtrace.cu:227) = origin of the pending shadow ray
+    float4 *accD;        // direct.xyz, at the HOME slot
+    float4 *accI;        // indirect.xyz, at the home slot
+    float4 *nee[2];      // pending NEE contribution.xyz, w = the bits of wfNeeTag(home, kind)
+    float4 *sht[2];      // shadow-ray target.xyz
+    uint2 *rng[2];       // {scramble, ptr}
+    int4 *hit;           // {primId, bary.x, bary.y, shading class of the hit's material}
     int *rayq[2];
     int *shadowq;
     int *litq[2];     // path slots of rays that look literal-class (bit 30: a shadow ray); trace(k) starts them first, one per wave
@@ -72,38 +80,59 @@ struct WaveWorkspace {
     WaveCounters *ctr;
 };
 
-// The ray trace(k) walks for path slot p, and how far: the shadow ray of the slot's pending NEE sample (prevPos -> sht), or its
+// nee.w: the home slot above two bits of kind, 0 → the contribution goes to direct, 1 → to indirect, 2 → nothing to add (slots stay
+// below 2^30: kWfLitShadow).  It travels as a float's bits through loads and stores only.
+constexpr unsigned kWfNeeNone = 2u;
+RD_DEV float wfNeeTag(int home, unsigned kind) { return __uint_as_float(((unsigned)home << 2) | kind); }
+// the addition sampleDirectLight's caller makes (pathtrace.cu:201-207) once the shadow ray of a pending NEE sample `n` ended unoccluded
+RD_DEV void wfAddNee(const WaveWorkspace &w, float4 n) {
+    const unsigned tag = __float_as_uint(n.w), kind = tag & 3u;
+    if (kind == kWfNeeNone) return;
+    float4 *acc = (kind == 0u ? w.accD : w.accI) + (tag >> 2);
+    const float4 a = *acc;
+    *acc = make_float4(a.x + n.x, a.y + n.y, a.z + n.z, 0.f);
+}
+
+// The ray trace(k) walks for path slot p of set `set` = k & 1, and how far: the shadow ray of the slot's pending NEE sample (prevPos -> sht), or its
 // extension ray as shade(k-1) / raygen stored it.  k_wf_trace builds every ray here, so the workgroup's first list and the lane
 // that meets the same entry classify one and the same ray.
-RD_DEV Ray wfSlotRay(const WaveWorkspace &w, int p, bool shadow, float &limit) {
+RD_DEV Ray wfSlotRay(const WaveWorkspace &w, int set, int p, bool shadow, float &limit) {
     if (shadow) {
-        const float4 x = w.prevPos[p], y = w.sht[p];
+        const float4 x = w.prevPos[set][p], y = w.sht[set][p];
         return shadowRay(mk3(x.x, x.y, x.z), mk3(y.x, y.y, y.z), limit);
     }
-    const float4 o = w.ro[p], d = w.rd[p];
+    const float4 o = w.ro[set][p], d = w.rd[set][p];
     limit = 3.402823466e+38f;
     return Ray{mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z)};
 }
 
-// Path slot p as pathStep sees it (path_step.h): every getter is a load from the slot's record, every setter a store to it.
+// A record of stage k as pathStep sees it (path_step.h): every getter is a load from slot p of the set the stage reads, every setter a
+// store to the record's fresh slot q of the other set; the accumulators are at the path's home slot.  Home is p itself at k = 0 and
+// arrives with throughput() later, which pathStep asks for before every addIndirect, setNee and setRay of k > 0.
 struct WaveSlotPath {
     const WaveWorkspace &w;
-    const int p;
-    const bool delta;  // rd[p].w, which the caller has loaded with the ray's direction
-    RD_DEV v3 throughput() const { const float4 t = w.thr[p]; return mk3(t.x, t.y, t.z); }
-    RD_DEV float samplePdf() const { return w.ro[p].w; }
+    const int rs, p;   // read: set, slot
+    const int wr, q;   // write: set, slot
+    int home;
+    const bool delta;  // rd[rs][p].w, which the caller has loaded with the ray's direction
+    RD_DEV v3 throughput() {
+        const float4 t = w.thr[rs][p];
+        home = __float_as_int(t.w);
+        return mk3(t.x, t.y, t.z);
+    }
+    RD_DEV float samplePdf() const { return w.ro[rs][p].w; }
     RD_DEV bool sampleDelta() const { return delta; }
-    RD_DEV v3 prevPos() const { const float4 c = w.prevPos[p]; return mk3(c.x, c.y, c.z); }
-    RD_DEV void setDirect(v3 v) { w.accD[p] = make_float4(v.x, v.y, v.z, 0.f); }
-    RD_DEV void addIndirect(v3 v) { const float4 a = w.accI[p]; w.accI[p] = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, 0.f); }
-    RD_DEV Sampler rng(const DScene &s) const { const uint2 r = w.rng[p]; return Sampler{s.sobol, r.x, (int)r.y}; }
-    RD_DEV void setNee(v3 c, float nw) { w.nee[p] = make_float4(c.x, c.y, c.z, nw); }
-    RD_DEV void setPrevPos(v3 x) { w.prevPos[p] = make_float4(x.x, x.y, x.z, 0.f); }
+    RD_DEV v3 prevPos() const { const float4 c = w.prevPos[rs][p]; return mk3(c.x, c.y, c.z); }
+    RD_DEV void setDirect(v3 v) { w.accD[home] = make_float4(v.x, v.y, v.z, 0.f); }
+    RD_DEV void addIndirect(v3 v) { const float4 a = w.accI[home]; w.accI[home] = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, 0.f); }
+    RD_DEV Sampler rng(const DScene &s) const { const uint2 r = w.rng[rs][p]; return Sampler{s.sobol, r.x, (int)r.y}; }
+    RD_DEV void setNee(v3 c, float nw) { w.nee[wr][q] = make_float4(c.x, c.y, c.z, wfNeeTag(home, nw < 0.f ? kWfNeeNone : (nw == 0.f ? 0u : 1u))); }
+    RD_DEV void setPrevPos(v3 x) { w.prevPos[wr][q] = make_float4(x.x, x.y, x.z, 0.f); }
     RD_DEV void setRay(const Ray &ray, float pdf, bool deltaSample, v3 throughput, const Sampler &rng) {
-        w.ro[p] = make_float4(ray.o.x, ray.o.y, ray.o.z, pdf);
-        w.rd[p] = make_float4(ray.d.x, ray.d.y, ray.d.z, deltaSample ? 1.f : 0.f);
-        w.thr[p] = make_float4(throughput.x, throughput.y, throughput.z, 0.f);
-        w.rng[p] = make_uint2(rng.scramble, (unsigned)rng.ptr);
+        w.ro[wr][q] = make_float4(ray.o.x, ray.o.y, ray.o.z, pdf);
+        w.rd[wr][q] = make_float4(ray.d.x, ray.d.y, ray.d.z, deltaSample ? 1.f : 0.f);
+        w.thr[wr][q] = make_float4(throughput.x, throughput.y, throughput.z, __int_as_float(home));
+        w.rng[wr][q] = make_uint2(rng.scramble, (unsigned)rng.ptr);
     }
 };
 
@@ -203,16 +232,16 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
     const unsigned b = group / nLocal, blockLocal = group - b * nLocal;
     Pix px = mapPixel(pm, inRange ? blockLocal * (unsigned)parts + (unsigned)part : 0xffffffffu / 64u, lane);
     bool valid = px.valid && inRange;
-    int p = int(group * 64u + lane);  // path slot = work index (fixed for the launch)
+    int p = int(group * 64u + lane);  // the path's home slot = work index; its slot in stage 0 as well
     bool listed = false;
     if (valid) {
         Sampler rng = makeSeededRandomEngine(int(((unsigned)looper + b) % (unsigned)kSobolRows), px.index, 0, s.sobol);
         Ray ray = cameraSample(cam, px.x, px.y, sample4D(rng));
-        w.ro[p] = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.f);
-        w.rd[p] = make_float4(ray.d.x, ray.d.y, ray.d.z, 0.f);
+        w.ro[0][p] = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.f);
+        w.rd[0][p] = make_float4(ray.d.x, ray.d.y, ray.d.z, 0.f);
         w.accD[p] = make_float4(0.f, 0.f, 0.f, 0.f);
         w.accI[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-        w.rng[p] = make_uint2(rng.scramble, (unsigned)rng.ptr);
+        w.rng[0][p] = make_uint2(rng.scramble, (unsigned)rng.ptr);
         // Primary rays that LOOK literal-class (the hint k_wf_shade uses for the rays it emits) go on stage 0's first list, so that a
         // workgroup of trace(0) traces them before anything else instead of one wave meeting them late (stage 0 was where the last
         // launches above 1 ms were: profiles/r03_w_teapots_trace_stage_time_histogram.txt).  A handful per frame: one atomic each.
@@ -245,8 +274,8 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
 // shade(k-1) emitted (shadowq), and both the static first packets and the shared head hand items out in increasing order.  A shadow
 // ray ends at its first accepted triangle within its segment; an extension ray walks to its closest hit, several times as far.  With
 // the shadow rays first (the order until DESIGN 5b, "Extension rays first") every stage ended on its longest rays with nothing left to
-// refill the lanes they leave idle.  Nothing reads an order: a shadow ray adds to accD / accI of its own slot, an extension ray writes
-// hit of its own.  1: the old order (measurements).  Teapots 1080p, 8 bounces, sorted, one pipeline, 1 / 0: 8.41 / 7.94 ms per frame,
+// refill the lanes they leave idle.  Nothing reads an order: a shadow ray adds to accD / accI of its path's home slot, an extension ray
+// writes hit of its own slot.  1: the old order (measurements).  Teapots 1080p, 8 bounces, sorted, one pipeline, 1 / 0: 8.41 / 7.94 ms per frame,
 // stages 1-8 of this kernel 6.31 / 5.80 ms; config 5's scene at 4K 33.04 / 32.59 ms (profiles/wf_order/)
 #ifndef RD_WF_SHADOW_FIRST
 #define RD_WF_SHADOW_FIRST 0
@@ -290,6 +319,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
     const int nRay = c->rayCount[k].v;
     const int total = nShadow + nRay;
     const int *rayq = w.rayq[k & 1];
+    const int set = k & 1;  // the state shade(k-1) / raygen wrote (WaveWorkspace)
     WalkStats ws{0, 0};
     unsigned nClosest = 0, nAny = 0, nHits = 0;
     const int end = s.bvhSize;
@@ -340,7 +370,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
         const bool sh = (e & kWfLitShadow) != 0;
         const int pp = e & (kWfLitShadow - 1);
         float lim;
-        const Ray ray = wfSlotRay(w, pp, sh, lim);
+        const Ray ray = wfSlotRay(w, set, pp, sh, lim);
         const RaySlab urs = makeRaySlab(ray);
         if (urs.cls == 0 || end == 0) continue;  // the hint did not hold: a lane takes this entry below
         const NodeRec *un = s.nodes[getMTBVHId(-ray.d)];
@@ -348,12 +378,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
         if (threadIdx.x == 0) {  // the record of the finished ray (as in the retire step of the loop below)
             if (sh) {
                 nAny++;
-                const float4 n = w.nee[pp];
-                if (!ct.found && n.w >= 0.f) {  // the addition sampleDirectLight's caller makes (pathtrace.cu:201-207)
-                    float4 *acc = n.w == 0.f ? w.accD : w.accI;
-                    const float4 a = acc[pp];
-                    acc[pp] = make_float4(a.x + n.x, a.y + n.y, a.z + n.z, 0.f);
-                }
+                if (!ct.found) wfAddNee(w, w.nee[set][pp]);
             } else {
                 nClosest++;
                 const bool hit = ct.hitPrim != -1;
@@ -421,7 +446,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
         RD_WF_STAMP_DRY();
         if (doStart) {
             if (p >= 0) {  // else: an off-frame slot of bounce 0, nothing to trace
-                const Ray ray = wfSlotRay(w, p, isShadow, tmax);
+                const Ray ray = wfSlotRay(w, set, p, isShadow, tmax);
                 if (isShadow) nAny++;
                 else nClosest++;
                 rs = makeRaySlab(ray);
@@ -563,16 +588,7 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
         if (doneM != 0ull && __popcll(doneM) * 64 >= (__popcll(doneM) + __popcll(__ballot(alive))) * RD_WF_FINISH_MIN)
         if (!alive && p >= 0) {
             if (isShadow) {
-                float4 n = w.nee[p];
-                if (!occluded && n.w >= 0.f) {  // the addition sampleDirectLight's caller makes (pathtrace.cu:201-207)
-                    if (n.w == 0.f) {
-                        float4 a = w.accD[p];
-                        w.accD[p] = make_float4(a.x + n.x, a.y + n.y, a.z + n.z, 0.f);
-                    } else {
-                        float4 a = w.accI[p];
-                        w.accI[p] = make_float4(a.x + n.x, a.y + n.y, a.z + n.z, 0.f);
-                    }
-                }
+                if (!occluded) wfAddNee(w, w.nee[set][p]);
             } else {
                 bool hit = hitPrim != -1;
                 if (hit) nHits++;
@@ -611,7 +627,7 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
         const int n = c->rayCount[k].v;
         const int *hitq = w.rayq[k & 1];
         // queue entries of the packet's chunks, held until its last chunk has been shaded, then appended together
-        int pendP[kShadeChunks], pendQ[kShadeChunks];  // path slot; its ray-queue entry (-2 - slot: trace(k+1) has it on its first list)
+        int pendP[kShadeChunks], pendQ[kShadeChunks];  // the record's new slot; its ray-queue entry (-2 - slot: trace(k+1) has it on its first list)
         bool pendShadow[kShadeChunks], pendRay[kShadeChunks];
 #pragma unroll
         for (int j = 0; j < kShadeChunks; j++) {
@@ -670,6 +686,9 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
             bool active = sorted ? (subNow + lane < packetEnd) : (item < n);
             bool emitShadow = false, emitRay = false, litShadow = false, litRay = false, rayFirst = false;
             int p = -1;
+            // the record's slot in stage k + 1 if its path goes on: its position in this stage's processing order (the queue index, or
+            // the place in class order inside the packet), unique and below n (WaveWorkspace)
+            const int q = base + subNow + lane;
             if (active) {
                 p = sorted ? mySorted[subNow + lane] : hitq[item];
                 if (p <= -2) p = -2 - p;  // (see the binning above)
@@ -677,13 +696,13 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
             }
             if (active) {
                 const int4 h = w.hit[p];
-                const float4 rdw = w.rd[p];
-                WaveSlotPath st{w, p, rdw.w != 0.f};
+                const float4 rdw = w.rd[k & 1][p];
+                WaveSlotPath st{w, k & 1, p, (k + 1) & 1, q, p, rdw.w != 0.f};
                 const PathStepResult r = pathStep(s, k, maxDepth, h.x, mk2(__int_as_float(h.y), __int_as_float(h.z)), mk3(rdw.x, rdw.y, rdw.z), st);
                 // the rays go to trace(k+1)'s queues below.  The two hints (trace classifies the ray it builds): some component of the
                 // direction below 1.1e-6 of its length
                 if (r.shadow) {
-                    w.sht[p] = make_float4(r.shadowTo.x, r.shadowTo.y, r.shadowTo.z, 0.f);
+                    w.sht[(k + 1) & 1][q] = make_float4(r.shadowTo.x, r.shadowTo.y, r.shadowTo.z, 0.f);
                     emitShadow = true;
                     const v3 dl = r.shadowTo - r.shadowFrom;
                     const float l2 = dot(dl, dl) * 1.21e-12f;
@@ -705,7 +724,7 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
                     if (lane == 0) at = atomicAdd(lc, __popcll(m));
                     at = __shfl(at, 0, 64) + __popcll(m & laneMaskLt());
                     if (pred && at < w.litCap) {  // beyond the list's capacity the ray stays in its ordinary queue
-                        lq[at] = kind == 0 ? (p | kWfLitShadow) : p;
+                        lq[at] = kind == 0 ? (q | kWfLitShadow) : q;
                         if (kind == 0) emitShadow = false;  // nobody else reads the shadow queue
                         else rayFirst = true;  // the ray queue is also shade(k+1)'s list of hits: the entry stays, marked as traced
                     }
@@ -716,8 +735,8 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
 #pragma unroll
                 for (int jj = 0; jj < kShadeChunks; jj++)
                     if (jj == j) {
-                        pendP[jj] = p;
-                        pendQ[jj] = rayFirst ? -2 - p : p;
+                        pendP[jj] = q;
+                        pendQ[jj] = rayFirst ? -2 - q : q;
                         pendShadow[jj] = emitShadow;
                         pendRay[jj] = emitRay;
                     }

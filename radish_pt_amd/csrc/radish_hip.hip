@@ -45,10 +45,10 @@ constexpr int kWfPartsDefault = 1;  // ... by default: see wavefrontPathTrace
 constexpr size_t kWfStripBudget = size_t(512) << 20;
 // rdh_path_trace_samples: what one pass of the wavefront pipeline may hold.  Fewer than 2^30 path slots (the queues encode
 // -2 - slot, and bit 30 marks a shadow ray on the first lists), and at most kWfSampleBudget bytes of them at kWfSlotBytes each
-// (152 B of path state + three queue entries; the sub-frame workspaces, two halves, add as much again).  kWfSamplesPerPass is the
+// (256 B of path state, the riding 104 B twice, + three queue entries; the sub-frame workspaces, two halves, add as much again).  kWfSamplesPerPass is the
 // library's choice within both (samplesPerPass = 0; measured: DESIGN 5f).
 constexpr long long kWfMaxSlots = 1ll << 30;
-constexpr size_t kWfSlotBytes = 164;
+constexpr size_t kWfSlotBytes = 268;
 constexpr size_t kWfSampleBudget = size_t(4) << 30;
 constexpr int kWfSamplesPerPass = 16;
 
@@ -760,8 +760,11 @@ int wfAlloc(rdh_ctx *c, T **out, size_t count) {
     return RDH_OK;
 }
 
-// Workspace for the wavefront pipeline: 152 B of path state + the ray / shadow queue entries per path slot, per sub-frame, plus
-// the two literal-class lists (litq) of kWfLitCap entries.  `samples`: how many samples of every pixel a launch carries.
+// Workspace for the wavefront pipeline: 256 B of path state + the ray / shadow queue entries per path slot, per sub-frame, plus
+// the two literal-class lists (litq) of kWfLitCap entries.  The state is 48 B that stay at the path's home slot (accD, accI, hit)
+// and 104 B that ride with it (ro rd thr prevPos nee sht rng), which every bounce writes afresh into the other of two sets
+// (kernels_wave.h, WaveWorkspace): the second set is +104 B per slot, +215 MB for workspace 0 at 1080p and about +1.7 GB over the
+// three workspaces at 4K.  `samples`: how many samples of every pixel a launch carries.
 int wavefrontEnsure(rdh_ctx *c, const PixelMap &pm, int samples) {
     long long slots = (long long)pm.numBlocks * 64 * samples;  // workspace 0: the whole frame; 1 and 2: a third each (+ a block), sized for half
     if (c->wfCapacity >= slots) return RDH_OK;
@@ -774,10 +777,14 @@ int wavefrontEnsure(rdh_ctx *c, const PixelMap &pm, int samples) {
     for (int h = 0; h < kWfParts; h++) {
         WaveWorkspace &w = c->wf[h];
         const size_t n = h == 0 ? n0 : n1;  // workspace 0 also serves the one-pipeline mode (whole frame)
-        int rc;
-        if ((rc = wfAlloc(c, &w.ro, n)) || (rc = wfAlloc(c, &w.rd, n)) || (rc = wfAlloc(c, &w.thr, n)) ||
-            (rc = wfAlloc(c, &w.prevPos, n)) || (rc = wfAlloc(c, &w.accD, n)) || (rc = wfAlloc(c, &w.accI, n)) ||
-            (rc = wfAlloc(c, &w.nee, n)) || (rc = wfAlloc(c, &w.sht, n)) || (rc = wfAlloc(c, &w.rng, n)) ||
+        int rc = RDH_OK;
+        for (int set = 0; set < 2 && rc == RDH_OK; set++) {
+            if ((rc = wfAlloc(c, &w.ro[set], n)) || (rc = wfAlloc(c, &w.rd[set], n)) || (rc = wfAlloc(c, &w.thr[set], n)) ||
+                (rc = wfAlloc(c, &w.prevPos[set], n)) || (rc = wfAlloc(c, &w.nee[set], n)) || (rc = wfAlloc(c, &w.sht[set], n)) ||
+                (rc = wfAlloc(c, &w.rng[set], n)))
+                return rc;
+        }
+        if ((rc = wfAlloc(c, &w.accD, n)) || (rc = wfAlloc(c, &w.accI, n)) ||
             (rc = wfAlloc(c, &w.hit, n)) || (rc = wfAlloc(c, &w.rayq[0], n)) || (rc = wfAlloc(c, &w.rayq[1], n)) ||
             (rc = wfAlloc(c, &w.shadowq, n)) || (rc = wfAlloc(c, &w.ctr, 1)) || (rc = wfAlloc(c, &w.litq[0], (size_t)kWfLitCap)) ||
             (rc = wfAlloc(c, &w.litq[1], (size_t)kWfLitCap)))
