@@ -873,13 +873,16 @@ class Context:
         return out
 
     def debug_wf_stamps(self):
-        """uint64 [stages, waves, 3] (entry, queue dry, exit; 100 MHz ticks) of the last wavefront pass's trace stages: a
-        -DRD_WF_STAMPS build via RADISH_HIP_LIB.  (Bound here, not in lib(): RADISH_HIP_LIB may name a build from before this entry.)"""
+        """uint64 [stages, waves, 6] of the last wavefront pass's trace stages: entry, queue dry, exit, list loop left (100 MHz
+        ticks), 1 + the reserved items the wave held unstarted when the shared head was dry, and 1 + the stage's list entries
+        (kernels_wave.h, kWfStampKinds): a
+        -DRD_WF_STAMPS build of this tree via RADISH_HIP_LIB.  (Bound here, not in lib(): RADISH_HIP_LIB may name a build from
+        before this entry.)"""
         fn = lib().rdh_debug_wf_stamps
         fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], C.c_int32
         stages, waves = C.c_int32(0), C.c_int32(0)
         self.check(fn(self.h, None, 0, C.byref(stages), C.byref(waves)))
-        out = np.zeros((stages.value, waves.value, 3), dtype=np.uint64)
+        out = np.zeros((stages.value, waves.value, 6), dtype=np.uint64)
         self.check(fn(self.h, out.ctypes.data, out.size, C.byref(stages), C.byref(waves)))
         return out
 

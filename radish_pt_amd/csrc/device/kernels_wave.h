@@ -76,6 +76,7 @@ struct WaveWorkspace {
 #ifdef RD_WF_STAMPS  // diagnostic build only: k_wf_trace's per-wave wall-clock stamps, [stage][logical wave][kWfStampKinds]; null: none
     unsigned long long *stamps;
     int stampWaves;   // logical waves of the trace grid
+    int stampStages;  // stages of the pass; behind their stamps lies one word per stage: the shared head has run dry (RD_WF_STAMP_HELD)
 #endif
     WaveCounters *ctr;
 };
@@ -172,9 +173,12 @@ RD_DEV void waveAppendN(const bool (&pred)[kShadeChunks], const int (&item)[kSha
 }
 
 // Work distribution for the persistent kernels.  Same-address returning atomics serialise chip-wide at ~12 ns each
-// (MI355X_MICROARCH.md "dequeue"/"fanin"), so (a) every wave's FIRST packet is fixed by its LOGICAL wave g — wave g takes
-// items [g*kPacket, (g+1)*kPacket) — and the shared head only hands out what lies beyond gridWaves*kPacket, and (b) a pull
-// reserves kPacket = 128 items.  Heads and tickets are zeroed once per frame by the counters memset.
+// (MI355X_MICROARCH.md "dequeue"/"fanin"), so (a) the FIRST share of the work is fixed by the logical index and costs no atomic,
+// and the shared head only hands out what lies beyond the fixed shares, and (b) a pull reserves many items at once.
+// k_wf_shade: wave g's first packet is items [g*packet, (g+1)*packet), and a pull (wavePull) reserves one packet of 256..1 024
+// records for the wave, behind gridWaves*packet.  k_wf_trace: packets of kPacket = 128 items; only the waves of workgroups
+// WITHOUT list duty own a first packet, and a pull (tracePull) reserves the next one behind those (see the kernel's header).
+// Heads and tickets are zeroed once per frame by the counters memset.
 //
 // The logical wave comes from the workgroup's ticket, taken in the order the workgroups become resident, not from blockIdx:
 // a launch is not alone on the chip (the sub-frame pipelines each launch the whole resident grid, and two of them may share a
@@ -182,7 +186,7 @@ RD_DEV void waveAppendN(const bool (&pred)[kShadeChunks], const int (&item)[kSha
 // their slots.  With blockIdx those late workgroups would start their fixed share — first packets, literal-class list entries —
 // late; with tickets whatever starts late takes what nobody has taken yet.  Cost: one returning atomic per WORKGROUP, spread
 // over kTicketShards = 8 counters (workgroup b uses counter b % 8, the XCD the dispatcher dealt it to), not one per wave.
-constexpr int kPacket = 128;
+constexpr int kPacket = 128;  // k_wf_trace: items a wave reserves for itself, fixed first packet and pull alike
 RD_DEV int gridWaves() { return int(gridDim.x * (blockDim.x >> 6)); }
 // The workgroup's logical index in [0, gridDim.x), a permutation of blockIdx.x: shard x holds exactly the workgroups
 // b = x + S t < gridDim.x (S = kTicketShards), and its t-th ticket becomes x + S t.  Every thread of the workgroup must call it (barrier).
@@ -197,10 +201,18 @@ RD_DEV int workgroupTicket(WaveCounter *tickets) {
 }
 // (wave-uniform, so kept in a scalar register: the VGPR budget of k_wf_trace has no room for it)
 RD_DEV int logicalWave(int wg) { return __builtin_amdgcn_readfirstlane(int(wg * int(blockDim.x >> 6) + int(threadIdx.x >> 6))); }
-RD_DEV int wavePull(int *head, int packet = kPacket) {
+// k_wf_shade's pull: the next packet behind the waves' fixed first packets
+RD_DEV int wavePull(int *head, int packet) {
     int base = 0;
     if ((threadIdx.x & 63u) == 0u) base = atomicAdd(head, packet);
     return __shfl(base, 0, 64) + gridWaves() * packet;
+}
+// k_wf_trace's pull: the next packet behind `headBase`, the end of the stage's fixed first packets (which depends on how many
+// workgroups have list duty, so the caller says where it is).  Called with the whole wave active; the result is wave-uniform.
+RD_DEV int tracePull(int *head, int headBase) {
+    int base = 0;
+    if ((threadIdx.x & 63u) == 0u) base = atomicAdd(head, kPacket);
+    return __builtin_amdgcn_readlane(base, 0) + headBase;
 }
 // (Round 3 measured GUIDED self-scheduling — after the static packet a pull reserves an even share of half the items still
 // unreserved, 32..128 for k_wf_trace, 64..packet for k_wf_shade, since a stage hands every wave only two or three fixed packets —
@@ -260,10 +272,20 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
 }
 
 // ---- trace(k): closest hits of bounce k + shadow rays of bounce k (from shade(k-1)) ---------------------------
-// Persistent waves with LANE REFILL: a wave reserves 64 consecutive work items per atomic and hands them to lanes
+// Persistent waves with LANE REFILL: a wave reserves kPacket = 128 consecutive work items per atomic and hands them to lanes
 // one by one as their previous ray finishes, so a wave never idles behind its longest ray (rays of one packet differ
 // several-fold in visit count after the first bounce).  Shadow (any-hit) and extension (closest-hit) rays run through
 // one walker; a lane's kind only decides how it terminates.
+//
+// Hand-out ("A workgroup with list duty takes no fixed share").  G = gridDim.x, L = min(nLit, G): the workgroups with
+// tickets below L trace a list entry together first (list duty), and their waves own NO first packet: they go to the shared head
+// once the list is done, and leave if it is dry by then.  The waves of ticket t >= L own the packets 4 (t - L) .. 4 (t - L) + 3,
+// and the head hands out what lies behind 4 (G - L) packets.  Before (RD_WF_DUTY_SHARE=1: measurements) every wave owned a first
+// packet, duty or not, so a workgroup with a slow list ray started its 512 fixed items, the stage's lowest-numbered and longest
+// rays, when the others were finishing theirs.  Which lane traces an item changes no image and no counter.
+#ifndef RD_WF_DUTY_SHARE
+#define RD_WF_DUTY_SHARE 0
+#endif
 #ifndef RD_REFILL_MIN
 #define RD_REFILL_MIN 16  // refill once at least this many lanes are idle
 #endif
@@ -281,16 +303,25 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
 #define RD_WF_SHADOW_FIRST 0
 #endif
 // RD_WF_STAMPS (diagnostic build only, like RD_PERSIST_STAMPS): lane 0 of every wave stores wall_clock64() (100 MHz) into its own
-// slot of WaveWorkspace::stamps when it enters the kernel, when it first finds the stage's queue exhausted, and when it leaves —
-// plain stores, no shared counter.  The entry stamp is the reference the other two are read against (the earliest one of a stage is
-// the launch's start: scripts/wf_stage_tails.py).  The default build holds none of it.
-constexpr int kWfStampKinds = 3;  // entry, queue dry, exit
+// slot of WaveWorkspace::stamps when it enters the kernel, when it first finds the stage's queue exhausted, when it leaves, and when
+// it has left the list loop — plain stores, no shared counter.  The entry stamp is the reference the others are read against (the
+// earliest one of a stage is the launch's start: scripts/wf_stage_tails.py).  The fifth word is no time: 1 + the reserved items the
+// wave had not started at its first refill after the shared head had
+// passed the stage's last item; 0: it never came to a refill after that.  (The wave that finds the head dry says so in a word of
+// the stage's own behind the stamps, and a refill loads that word: polling the head itself, the line every pull's atomic goes
+// to, made the stamped frame 2.7 times as long.)  The sixth is 1 + the
+// stage's list entries (nLit), so that the reader knows which workgroups had list duty: those with tickets below it.  The default
+// build holds none of it.
+constexpr int kWfStampKinds = 6;  // entry, queue dry, exit, list loop left, 1 + items held when the head was dry, 1 + nLit
 #ifdef RD_WF_STAMPS
 #define RD_WF_STAMP(kind) do { if (stampAt && (threadIdx.x & 63u) == 0u) stampAt[kind] = wall_clock64(); } while (0)
-#define RD_WF_STAMP_DRY() do { if (exhausted && !stampedDry) { stampedDry = true; RD_WF_STAMP(1); } } while (0)
+#define RD_WF_STAMP_DRY() do { if (exhausted && !stampedDry) { stampedDry = true; RD_WF_STAMP(1); if (stampAt && (threadIdx.x & 63u) == 0u) *headDry = 1ull; } } while (0)
+#define RD_WF_STAMP_HELD(held) do { if (stampAt && !stampedHeld && *headDry != 0ull) { \
+        stampedHeld = true; const int h_ = (held); if ((threadIdx.x & 63u) == 0u) stampAt[4] = 1ull + (unsigned long long)h_; } } while (0)
 #else
 #define RD_WF_STAMP(kind) ((void)0)
 #define RD_WF_STAMP_DRY() ((void)0)
+#define RD_WF_STAMP_HELD(held) ((void)0)
 #endif
 #ifndef RD_WF_COOP_LONE  // a lone walking lane is walked by the whole wave (coopWalk): 0.5-1 % on either scene
 #define RD_WF_COOP_LONE 1
@@ -306,13 +337,23 @@ constexpr int kWfStampKinds = 3;  // entry, queue dry, exit
 #ifndef RD_WF_PAIR_WAVES
 #define RD_WF_PAIR_WAVES 1  // waves per SIMD the pair variant is held to (1: whatever its registers allow)
 #endif
+// ... and AT MOST (8: no bound): its registers are padded to that step, and the host holds its resident grid to as many workgroups
+// per CU (radish_hip.hip, wavefrontPathTrace: the runtime's occupancy query goes by the registers used, not the padded number).
+// The pair walk is slower with seven waves per SIMD than with six, and how many registers it needs moves between 71 and 75 with
+// unrelated edits of this kernel, across the step at 72: teapots 1080p, 8 bounces, one pipeline, the same hand-out at
+// 75 registers / six waves 7.52-7.56 ms a frame, at 71 / seven waves 8.51-8.54 (profiles/wf_handout/variants.txt)
+#ifndef RD_WF_PAIR_MAX_WAVES
+#define RD_WF_PAIR_MAX_WAVES 6
+#endif
 template <bool COUNT, bool PAIRS = false>
-__global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ? RD_WF_TRACE_WAVES : 1)) void k_wf_trace(DScene s, WaveWorkspace w, int k) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ? RD_WF_TRACE_WAVES : 1),
+                                                                      PAIRS && !COUNT ? RD_WF_PAIR_MAX_WAVES : 8))) void k_wf_trace(DScene s, WaveWorkspace w, int k) {
     WaveCounters *c = w.ctr;
     const int wg = workgroupTicket(c->traceTicket[k]);  // stands for blockIdx.x below (see wavePull)
 #ifdef RD_WF_STAMPS
     unsigned long long *const stampAt = w.stamps ? w.stamps + ((size_t)k * (size_t)w.stampWaves + (size_t)logicalWave(wg)) * kWfStampKinds : nullptr;
-    bool stampedDry = false;
+    volatile unsigned long long *const headDry = w.stamps ? w.stamps + (size_t)w.stampStages * (size_t)w.stampWaves * kWfStampKinds + k : nullptr;
+    bool stampedDry = false, stampedHeld = false;
     RD_WF_STAMP(0);
 #endif
     const int nShadow = (k > 0) ? c->shadowCount[k - 1].v : 0;
@@ -325,8 +366,14 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
     const int end = s.bvhSize;
     const int END = end;  // `node` of a finished walk (!PAIRS)
 
-    // wave-uniform reservation of work items; the first one is the logical wave's (see wavePull)
-    int resNext = logicalWave(wg) * kPacket, resEnd = resNext + kPacket;
+    // Fixed first packets and the start of the shared head (wave-uniform arithmetic; see the kernel's header).  A wave whose packet
+    // starts beyond the stage's items, or a duty workgroup's when the fixed packets cover the stage, has nothing to trace and never pulls.
+    const int nLit = c->litCount[k].v < w.litCap ? c->litCount[k].v : w.litCap;
+    const int dutyGroups = RD_WF_DUTY_SHARE ? 0 : (nLit < int(gridDim.x) ? nLit : int(gridDim.x));  // L
+    const bool duty = wg < dutyGroups;
+    const int headBase = (int(gridDim.x) - dutyGroups) * int(blockDim.x >> 6) * kPacket;
+    // the wave's own reservation of work items; the first one is its fixed packet
+    int resNext = duty ? headBase : (logicalWave(wg) - dutyGroups * int(blockDim.x >> 6)) * kPacket, resEnd = duty ? resNext : resNext + kPacket;
     bool exhausted = resNext >= total;
     if (resEnd > total) resEnd = total;
     RD_WF_STAMP_DRY();
@@ -364,7 +411,6 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
     WgTraceSharedT<256> &wgsh = lds.wg;
     int2 *const stk = lds.stack + (PAIRS ? int(threadIdx.x >> 6) * kPairLds * 64 : 0);
     int2 *const ovf = PAIRS ? reinterpret_cast<int2 *>(w.treeOvf) + (size_t)logicalWave(wg) * (size_t)w.treeOvfDepth * 64 : nullptr;
-    const int nLit = c->litCount[k].v < w.litCap ? c->litCount[k].v : w.litCap;
     for (int it = wg; it < nLit; it += int(gridDim.x)) {  // uniform over the workgroup
         const int e = w.litq[k & 1][it];
         const bool sh = (e & kWfLitShadow) != 0;
@@ -392,6 +438,10 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
             }
         }
     }
+    RD_WF_STAMP(3);
+#ifdef RD_WF_STAMPS
+    if (stampAt && (threadIdx.x & 63u) == 0u) stampAt[5] = 1ull + (unsigned long long)nLit;
+#endif
     if (PAIRS) __syncthreads();  // every wave is done with the workgroup trace's LDS
     bool firstRound = true;
     bool fromList = false;  // this lane's item of the first round came from the list: skip it if the workgroup has traced it above
@@ -414,11 +464,12 @@ __global__ __launch_bounds__(256, PAIRS && !COUNT ? RD_WF_PAIR_WAVES : (!COUNT ?
         unsigned long long idle = __ballot(!alive && !doStart && p < 0);
         int nIdle = __popcll(idle);
         if (!exhausted && nIdle >= RD_REFILL_MIN) {
+            RD_WF_STAMP_HELD(resEnd - resNext);
             int myRank = __popcll(idle & laneMaskLt());
             int taken = 0;  // items handed out so far in this refill (wave-uniform)
             while (taken < nIdle && !exhausted) {
                 if (resNext == resEnd) {
-                    resNext = wavePull(&c->traceHead[k].v);
+                    resNext = tracePull(&c->traceHead[k].v, headBase);
                     resEnd = resNext + kPacket;
                     if (resNext >= total) {
                         exhausted = true;

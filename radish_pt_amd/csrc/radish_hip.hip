@@ -816,6 +816,11 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
     int rq = RDH_OK;
     withBools([&](auto cnt, auto pr) { rq = residentGrid(c, k_wf_trace<cnt.value, pr.value>, 256, &traceRes); }, count, tree);
     if (rq || (rq = residentGrid(c, k_wf_shade, 256, &shadeRes))) return rq;
+    if (tree && !count) {  // the pair variant is held to RD_WF_PAIR_MAX_WAVES waves per SIMD = as many 256-thread workgroups per CU
+        int cus = 0;
+        if (int rc = cuCount(c, &cus)) return rc;
+        traceRes = std::min(traceRes, (unsigned)cus * (unsigned)RD_WF_PAIR_MAX_WAVES);
+    }
     // persistent grids: the whole resident grid for every sub-frame pipeline (two pipelines serialised on one hardware queue
     // then each run at full width; pipelines on different queues share the chip through the dispatcher), divided only between
     // the contexts that render side by side on this GPU (rdh_set_occupancy_share).  Only these grids are capped at kPersistentGrid,
@@ -845,12 +850,13 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
     }
 #ifdef RD_WF_STAMPS  // pipeline 0's trace stages stamp their waves (kernels_wave.h, RD_WF_STAMP); the others get no buffer
     {
-        const size_t stamps = (size_t)(maxDepth + 1) * traceGrid * 4 * kWfStampKinds;
+        const size_t stamps = (size_t)(maxDepth + 1) * traceGrid * 4 * kWfStampKinds + (size_t)(maxDepth + 1);  // + a word per stage
         if (int rc = grow(c, c->wfStamps, stamps, stamps * sizeof(unsigned long long), Busy::Device)) return rc;
         HIP_TRY(c, hipMemsetAsync(c->wfStamps.p, 0, stamps * sizeof(unsigned long long), c->stream));
         for (int h = 0; h < kWfParts; h++) {
             c->wf[h].stamps = h == 0 ? c->wfStamps.as<unsigned long long>() : nullptr;
             c->wf[h].stampWaves = (int)(traceGrid * 4);
+            c->wf[h].stampStages = maxDepth + 1;
         }
         c->wfStampStages = maxDepth + 1;
         c->wfStampWaves = (int)(traceGrid * 4);
