@@ -307,7 +307,7 @@ int rdh_debug_read_world(rdh_ctx *ctx, float *verticesOut, float *normalsOut);
  * before anything is enqueued, the scene unchanged: no scene RDH_ERR_NO_SCENE; an id out of range or listed twice, null pointers
  * with count > 0, a map id rdh_scene_upload would refuse (it must name one of the uploaded textures, -1, or -2 for a base
  * colour), an envPower rdh_scene_rebuild_lights would refuse: RDH_ERR_ARGS.  count == 0: RDH_OK, nothing enqueued.
- * Out of scope: giving triangles other material ids, which still takes rdh_scene_upload (textures: rdh_scene_set_texture, below).
+ * Giving triangles other material ids, or another triangle set: rdh_scene_set_geometry, below (textures: rdh_scene_set_texture).
  * rdh_build_light_list_device: the device twin of rdh_build_light_list (include/radish_host.h) — d_vertices float[3*numPrims][3],
  * d_materialIds int32[numPrims], d_materials Material[numMaterials] -> d_lightPrimIds int32[], d_lightUnitRadiance float[][3],
  * d_lightPower float[] (each with room for numPrims entries; the first *d_count are written) and *d_count, bit for bit what the
@@ -349,6 +349,37 @@ int rdh_build_light_list_device(rdh_ctx *ctx, const float *d_vertices, const int
 int rdh_scene_set_texture(rdh_ctx *ctx, int32_t texId, const float *d_texels, int32_t width, int32_t height);
 int rdh_scene_env_power(rdh_ctx *ctx, float *out);
 long long rdh_debug_read_textures(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
+/* ---- the triangle set replaced on the device -----------------------------------------------------------------------------
+ * rdh_scene_set_geometry: the uploaded scene's triangles are replaced by numPrims triangles from DEVICE arrays, all four required
+ * (the count may differ from the current one): d_vertices and d_normals float[3*numPrims][3], d_texcoords float[3*numPrims][2],
+ * d_materialIds int32[numPrims].  builder: RDH_BVH_SAH or RDH_BVH_LBVH; envPower as for rdh_scene_rebuild_lights.  Materials,
+ * textures, the environment map, the Sobol table and the camera stay.  With RDH_BVH_SAH the scene is then, bit for bit, what a
+ * fresh rdh_scene_upload of the same description gives (these arrays, the scene's current materials and textures, rdh_build_bvh's
+ * tree, rdh_build_light_list + rdh_build_alias_table; the alias table's NaN payloads aside): TriRec, AttrRec, shading classes, the
+ * six node arrays at the new stride with their pad records, the pairs (none past 2 048 levels), treeDepth and root box, the
+ * emissive-triangle list, LightRec, LightPre, alias table, lightSamplerLength and sumLightPowerInv.  With RDH_BVH_LBVH it is what
+ * that upload followed by rdh_scene_update_geometry_ex(..., RDH_BVH_LBVH) on the same vertices holds.
+ * One call: (1) one kernel over the caller's arrays counts the triangles of every material and flags a material id outside
+ * [0, numMaterials) and a coordinate that fails the upload's fabs(x) < 1e30f; the call waits for these 4 * (numMaterials + 2) bytes
+ * through pinned memory, its only host wait apart from growth, and a raised flag returns RDH_ERR_ARGS with the scene unchanged.
+ * (2) A count above what the scene's arrays hold (triangles, emitters, sampler entries: each tracked on its own) allocates the new
+ * arrays first and releases the old ones then, so a failed allocation leaves the scene as it was; growth waits for the stream and
+ * the side streams; a smaller count frees nothing.  (3) The records are packed, (4) the tree is built by `builder` as
+ * rdh_scene_update_geometry builds it, and (5) the emissive-triangle list and what rdh_scene_rebuild_lights(ctx, envPower) does
+ * follow, always: numLights is the host's sum of the new counts over the Light materials, so lightSamplerLength = numLights (+ 1
+ * with an environment map) changes with the call; no light and no environment map: length 0, sumLightPowerInv 0.
+ * Dropped, as an upload drops them: the refit plan, the persistent block order, the object table with its rest pose and world
+ * arrays (a pose returns RDH_ERR_STATE until rdh_scene_set_objects is called again).  Kept: motion tracking if it was on — the
+ * buffer follows the count and is marked "previous == current", because triangle p of the old set has no counterpart, so the next
+ * G-buffer render writes the reference's plane — and ReSTIR reservoirs: call rdh_restir_init, as after every other edit that
+ * changes the lights.  Refused before anything is enqueued: no scene RDH_ERR_NO_SCENE; a null pointer, numPrims <= 0 or above
+ * 1 << 29, six node arrays of 4 GiB or more, an unknown builder, an envPower rdh_scene_rebuild_lights would refuse: RDH_ERR_ARGS.
+ * rdh_debug_read_geometry: test access: which = 0 the TriRec bytes (numPrims x 48), 1 the AttrRec bytes (numPrims x 64), 2 the
+ * shading classes (numPrims bytes), 3 the context's per-material triangle counts (numMaterials x int32).  Returns the byte size
+ * (hostOut NULL: only that) or a negative RDH_ERR_*.  Blocking. */
+int rdh_scene_set_geometry(rdh_ctx *ctx, const float *d_vertices, const float *d_normals, const float *d_texcoords,
+                           const int32_t *d_materialIds, int32_t numPrims, int builder, float envPower);
+long long rdh_debug_read_geometry(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
 /* Replaces DevScene::destroy (src/scene.cpp:553-574). */
 int rdh_scene_free(rdh_ctx *ctx);
 /* The `Camera cam` kernel argument of every reference kernel (State::scene->camera, src/pathtrace.cu:356). */

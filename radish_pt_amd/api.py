@@ -74,6 +74,7 @@ EXPORTS = [
     "rdh_scene_set_objects", "rdh_scene_pose_objects", "rdh_debug_read_world",
     "rdh_scene_set_materials", "rdh_build_light_list_device",
     "rdh_scene_set_texture", "rdh_scene_env_power", "rdh_debug_read_textures",
+    "rdh_scene_set_geometry", "rdh_debug_read_geometry",
 ]
 
 
@@ -211,6 +212,8 @@ def lib():
             "rdh_scene_set_texture": ([vp, i32, vp, i32, i32], i32),
             "rdh_scene_env_power": ([vp, C.POINTER(C.c_float)], i32),
             "rdh_debug_read_textures": ([vp, i32, vp, i64], i64),
+            "rdh_scene_set_geometry": ([vp, vp, vp, vp, vp, i32, i32, C.c_float], i32),
+            "rdh_debug_read_geometry": ([vp, i32, vp, i64], i64),
         }
         for name, (args, res) in sig.items():
             fn = getattr(l, name)
@@ -520,6 +523,46 @@ class Context:
         if which == 0:
             return out.view(np.float32)
         return out.view(L.BINOMIAL_DTYPE) if which == 1 else out
+
+    # ---- the triangle set replaced on the device ----
+    def set_geometry(self, vertices, normals, texcoords, material_ids, builder="sah", env_power=0.0):
+        """Replace the uploaded scene's triangles (rdh_scene_set_geometry): vertices / normals float32 cuda tensors of 9*N floats,
+        texcoords of 6*N floats, material_ids an int32 cuda tensor [N]; N >= 1 may differ from the uploaded count.  Materials,
+        textures, the environment map and the camera stay; the tree is built on the device with `builder`, and the light list and
+        sampler are derived again (env_power as for rebuild_lights).  With "sah" the scene then equals, bit for bit, a fresh
+        upload_scene of the edited description; with "lbvh" that upload followed by update_geometry(..., builder="lbvh").  The
+        object table is dropped (call set_objects again before a pose).  Waits once for the check of the arrays.  The
+        reference-style shim (DevScene / Scene) has no counterpart: it uploads."""
+        b = _builder("set_geometry", builder)
+        torch = _torch()
+        if getattr(self, "_num_prims", None) is None:
+            raise RadishError("set_geometry: no scene uploaded")
+        if not isinstance(material_ids, torch.Tensor) or material_ids.numel() == 0:
+            raise RadishError("set_geometry: material_ids must be a tensor of N >= 1 int32")
+        n = material_ids.numel()
+        for t, name, per in ((vertices, "vertices", 9), (normals, "normals", 9), (texcoords, "texcoords", 6)):
+            if not isinstance(t, torch.Tensor) or t.numel() != per * n:
+                got = t.numel() if isinstance(t, torch.Tensor) else type(t).__name__
+                raise RadishError(f"set_geometry: {name} must hold {per}*{n} floats ({n} material ids), got {got}")
+        vp = self._ptr(vertices, 9 * n, "set_geometry vertices")
+        np_ = self._ptr(normals, 9 * n, "set_geometry normals")
+        tp = self._ptr(texcoords, 6 * n, "set_geometry texcoords")
+        ip = self._ptr(material_ids, n, "set_geometry material_ids", torch.int32)
+        self.check(lib().rdh_scene_set_geometry(self.h, vp, np_, tp, ip, n, b, float(env_power)))
+        self._num_prims = int(n)
+
+    def debug_read_geometry(self, which):
+        """Blocking test access (rdh_debug_read_geometry): 0 -> TriRec bytes, 1 -> AttrRec bytes, 2 -> the shading classes (uint8),
+        3 -> the per-material triangle counts (int32)."""
+        n = lib().rdh_debug_read_geometry(self.h, which, None, 0)
+        if n < 0:
+            self.check(int(n))
+        out = np.zeros(n, np.uint8)
+        if n:
+            rc = lib().rdh_debug_read_geometry(self.h, which, out.ctypes.data, n)
+            if rc < 0:
+                self.check(int(rc))
+        return out.view(np.int32) if which == 3 else out
 
     # ---- moving geometry: objects posed on the device (DESIGN 11f) ----
     def set_objects(self, sd=None, objects=None, rest_vertices=None, rest_normals=None):

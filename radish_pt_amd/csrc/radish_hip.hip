@@ -36,6 +36,7 @@
 #include "device/kernels_pose.h"
 #include "device/kernels_materials.h"
 #include "device/kernels_textures.h"
+#include "device/kernels_geometry.h"
 
 using namespace rd;
 
@@ -157,6 +158,10 @@ struct SceneState {
                                          // edit, or by rdh_scene_env_power)
     float *envRowSin = nullptr;          // the environment map's row factors, the host's sinf((.5f + i) / height * PI): sent once
     bool envSumValid = false;            // envScratch's sums[0] is the power of the environment map as ds.texData holds it
+
+    // rdh_scene_set_geometry (kernels_geometry.h)
+    int primCap = 0;                     // triangles that ds.tris, ds.attrs, ds.primClass, the node allocation, the pairs and prevTris
+                                         // hold (the upload's count until a larger set arrives; never shrinks)
 };
 
 struct rdh_ctx {
@@ -270,6 +275,11 @@ struct rdh_ctx {
 
     // rdh_scene_set_texture (kernels_textures.h): the environment map's row factors on their way to SceneState::envRowSin
     StagePair rowStage{bufs};
+
+    // rdh_scene_set_geometry (kernels_geometry.h): k_geom_check's per-material counts and its two flags
+    GrowBuf dGeomCheck{bufs};            // materials (+ 2 ints)
+    GrowBuf hGeomCheck{bufs, true};      // its pinned host copy
+    hipEvent_t evGeomCheck = nullptr;    // recorded after that copy
 };
 
 namespace {
@@ -1283,6 +1293,7 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
     c->scene.ds.sumLightPowerInv = d->sumLightPowerInv;
     c->scene.lightCap = d->numLights;
     c->scene.lightLenCap = d->lightSamplerLength;
+    c->scene.primCap = N;
     c->scene.hostMats.assign(hm, hm + d->numMaterials);  // rdh_scene_set_materials edits these and counts emitters from them
     c->scene.matPrims.assign((size_t)d->numMaterials, 0);
     for (int p = 0; p < N; p++) c->scene.matPrims[(size_t)d->materialIds[p]]++;
@@ -2758,36 +2769,35 @@ int rewriteGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals,
     return RDH_OK;
 }
 
-// rdh_scene_update_geometry(_ex): the tree of `builder` (RDH_BVH_SAH or RDH_BVH_LBVH, checked by the caller).
-int updateGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights, int builder,
-                   const char *what) {
-    if (!c) return RDH_ERR_ARGS;
-    int rc = checkGeomArgs(c, what, d_vertices, lights);
-    if (rc) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int N = c->scene.ds.numPrims, S = c->scene.ds.bvhSize;
-    if ((rc = ensureTreeHeader(c))) return rc;
-    if ((rc = waitSideStreams(c))) return rc;
-    c->scene.planValid = false;  // a new topology: the next refit derives its plan again
-    if (!c->scene.ds.pairs && !c->scene.updPairs) {  // the upload had no pairs; an updated tree always has them
-        if ((rc = sceneAlloc(c, &c->scene.updPairs, sizeof(PairRec) * ((size_t)(S - 1) / 2 + 1)))) return rc;
+// The pairs an updated tree is written to: the upload's, or an array made here when the upload had none (an updated tree always has
+// them).  Sized for the scene's capacity, so that a later rdh_scene_set_geometry of more triangles within it finds room.
+int ensureUpdPairs(rdh_ctx *c, PairRec **out) {
+    if (!c->scene.ds.pairs && !c->scene.updPairs) {
+        const size_t capS = 2 * (size_t)c->scene.primCap - 1;
+        if (int rc = sceneAlloc(c, &c->scene.updPairs, sizeof(PairRec) * ((capS - 1) / 2 + 1))) return rc;
     }
-    PairRec *pairs = c->scene.updPairs ? c->scene.updPairs : const_cast<PairRec *>(c->scene.ds.pairs);
-    BvhWork w{};
-    LbvhWork L{};
-    if ((rc = builder == RDH_BVH_LBVH ? lbvhWorkspace(c, N, L, w) : bvhWorkspace(c, N, w))) return rc;
+    *out = c->scene.updPairs ? c->scene.updPairs : const_cast<PairRec *>(c->scene.ds.pairs);
+    return RDH_OK;
+}
+
+// The builder's workspace and the update's boxes + orderings for N triangles of d_vertices: everything of a tree build that can fail
+// for want of memory.
+int treeWorkspace(rdh_ctx *c, const float *d_vertices, int N, int builder, LbvhWork &L, BvhWork &w) {
+    const size_t S = 2 * (size_t)N - 1;
+    if (int rc = builder == RDH_BVH_LBVH ? lbvhWorkspace(c, N, L, w) : bvhWorkspace(c, N, w)) return rc;
     L.verts = d_vertices;
     w.verts = d_vertices;
-    if ((rc = growCarved(c, c->updTree, (size_t)N, Busy::Stream, [&](Carver &k) {
-            w.boxes = k.take<float>(sizeof(float) * 6 * (size_t)S);
-            for (int o = 0; o < 6; o++) w.nodes[o] = k.take<int>(sizeof(int) * 3 * (size_t)S);
-        })))
-        return rc;
+    return growCarved(c, c->updTree, (size_t)N, Busy::Stream, [&](Carver &k) {
+        w.boxes = k.take<float>(sizeof(float) * 6 * S);
+        for (int o = 0; o < 6; o++) w.nodes[o] = k.take<int>(sizeof(int) * 3 * S);
+    });
+}
 
-    if ((rc = rewriteGeometry(c, d_vertices, d_normals, lights))) return rc;
-
-    // the tree and what the upload derives from it
-    if ((rc = builder == RDH_BVH_LBVH ? launchLbvhBuild(c, L, w) : launchBvhBuild(c, w))) return rc;
+// The tree of `builder` and what the upload derives from it, on the context's stream: NodeRecs at stride S + 1, pairs, and the header
+// on its way to the host (settleTree).
+int enqueueTree(rdh_ctx *c, int builder, LbvhWork &L, BvhWork &w, PairRec *pairs) {
+    const int S = 2 * w.numPrims - 1;
+    if (int rc = builder == RDH_BVH_LBVH ? launchLbvhBuild(c, L, w) : launchBvhBuild(c, w)) return rc;
     const long long recs = 6ll * (S + 1);
     hipLaunchKernelGGL(k_bvh_noderecs, dim3((unsigned)((recs + 255) / 256)), dim3(256), 0, c->stream, (const float *)w.boxes, w,
                        const_cast<NodeRec *>(c->scene.ds.nodes[0]), S);
@@ -2795,6 +2805,25 @@ int updateGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, 
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->hTreeHdr.p, c->dTreeHdr.p, 3 * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
     return treeHeaderPending(c, false);  // an update's header (a refit's still pending is superseded): settle all of it
+}
+
+// rdh_scene_update_geometry(_ex): the tree of `builder` (RDH_BVH_SAH or RDH_BVH_LBVH, checked by the caller).
+int updateGeometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const rdh_light_update *lights, int builder,
+                   const char *what) {
+    if (!c) return RDH_ERR_ARGS;
+    int rc = checkGeomArgs(c, what, d_vertices, lights);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensureTreeHeader(c))) return rc;
+    if ((rc = waitSideStreams(c))) return rc;
+    c->scene.planValid = false;  // a new topology: the next refit derives its plan again
+    PairRec *pairs = nullptr;
+    if ((rc = ensureUpdPairs(c, &pairs))) return rc;
+    BvhWork w{};
+    LbvhWork L{};
+    if ((rc = treeWorkspace(c, d_vertices, c->scene.ds.numPrims, builder, L, w))) return rc;
+    if ((rc = rewriteGeometry(c, d_vertices, d_normals, lights))) return rc;
+    return enqueueTree(c, builder, L, w, pairs);
 }
 
 // rdh_build_bvh_device(_ex): the tree of a caller's soup into the caller's arrays, by `builder` (checked by the caller); `what` is
@@ -2954,7 +2983,7 @@ int rdh_scene_track_motion(rdh_ctx *c, int enable) {
     if ((enable != 0) == (c->scene.prevTris != nullptr)) return RDH_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     if (enable) {  // "previous == current": nothing to copy, the first update after this fills the buffer before any kernel reads it
-        if (int rc = sceneAlloc(c, &c->scene.prevTris, sizeof(TriRec) * (size_t)c->scene.ds.numPrims)) return rc;
+        if (int rc = sceneAlloc(c, &c->scene.prevTris, sizeof(TriRec) * (size_t)c->scene.primCap)) return rc;
     } else {
         HIP_TRY(c, hipStreamSynchronize(c->stream));  // a G-buffer render may still read the buffer (switching off is not a per-frame call)
         if (int rc = sceneRelease(c, &c->scene.prevTris)) return rc;
@@ -3036,11 +3065,16 @@ void launchAliasBuild(rdh_ctx *c, const float *d_values, int n, const AliasWork 
 }
 
 // What a light rebuild allocates: everything of it that can fail for want of memory, before the scene is touched.
-int prepareLightRebuild(rdh_ctx *c) {
+int prepareLightSums(rdh_ctx *c) {  // ... but the scratch, which rdh_scene_set_geometry sizes itself
     int rc;
     if ((rc = ensureTreeHeader(c))) return rc;
     if ((rc = grow(c, c->hLightSums, 2, 2 * sizeof(float), Busy::Nothing))) return rc;
     if (!c->evLights && (rc = newEvent(c, &c->evLights))) return rc;
+    return RDH_OK;
+}
+int prepareLightRebuild(rdh_ctx *c) {
+    int rc;
+    if ((rc = prepareLightSums(c))) return rc;
     if (!c->scene.lightScratch && (rc = sceneAlloc(c, &c->scene.lightScratch, aliasWorkBytes(c->scene.lightLenCap)))) return rc;
     return RDH_OK;
 }
@@ -3557,6 +3591,212 @@ long long rdh_debug_read_textures(rdh_ctx *c, int which, void *hostOut, long lon
         memcpy(hostOut, &envPower, 4);
         memcpy(static_cast<char *>(hostOut) + 4, n, 12);
     }
+    return bytes;
+}
+
+}  // extern "C"
+
+// ---- the triangle set replaced on the device (kernels_geometry.h) -------------------------------------------------------
+namespace {
+
+// Scene arrays that grow together: the fresh ones are all made before an old one goes, so a failed allocation leaves the scene as it
+// was.  add() allocates, commit() frees what the slots held and puts the fresh arrays there, abandon() frees the fresh ones.
+struct SceneRegrow {
+    rdh_ctx *c;
+    std::vector<void *> fresh;
+    std::vector<void **> slots;
+    template <typename T>
+    int add(T **slot, size_t bytes) {
+        void *p = nullptr;
+        if (int rc = sceneAlloc(c, &p, bytes)) return rc;
+        fresh.push_back(p);
+        slots.push_back(reinterpret_cast<void **>(const_cast<std::remove_const_t<T> **>(slot)));
+        return RDH_OK;
+    }
+    void abandon() {
+        for (void *&p : fresh) sceneRelease(c, &p, true);  // the failure's text stays in c->err
+        fresh.clear();
+        slots.clear();
+    }
+    void commit() {
+        for (size_t i = 0; i < fresh.size(); i++) {
+            sceneRelease(c, slots[i], true);
+            *slots[i] = fresh[i];
+        }
+        fresh.clear();
+        slots.clear();
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int rdh_scene_set_geometry(rdh_ctx *c, const float *d_vertices, const float *d_normals, const float *d_texcoords,
+                           const int32_t *d_materialIds, int32_t numPrims, int builder, float envPower) {
+    if (!c) return RDH_ERR_ARGS;
+    SceneState &s = c->scene;
+    if (!s.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_scene_set_geometry: no scene uploaded");
+    if (!d_vertices || !d_normals || !d_texcoords || !d_materialIds) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: null array");
+    if (numPrims <= 0) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: numPrims %d", numPrims);
+    if (builder != RDH_BVH_SAH && builder != RDH_BVH_LBVH) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: unknown builder %d", builder);
+    int rc = checkEnvPower(c, "rdh_scene_set_geometry", envPower);
+    if (rc) return rc;
+    if (numPrims > (1 << 29)) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: %d primitives", numPrims);
+    const int N = numPrims, S = 2 * N - 1;
+    if ((size_t)6 * ((size_t)S + 1) * sizeof(NodeRec) >= 0xffffffffull)  // as rdh_scene_upload: records are addressed by 32-bit byte offsets
+        return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: scene too large: %d BVH nodes", S);
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    // 1. the check pass: counts and flags of the caller's arrays, before anything of the scene is touched
+    const int numMaterials = (int)s.hostMats.size();
+    const size_t checkInts = (size_t)numMaterials + 2;
+    if ((rc = grow(c, c->dGeomCheck, checkInts, sizeof(int) * checkInts, Busy::Stream))) return rc;
+    if ((rc = grow(c, c->hGeomCheck, checkInts, sizeof(int) * checkInts, Busy::Nothing))) return rc;  // (every call has waited for its copy)
+    if (!c->evGeomCheck && (rc = newEvent(c, &c->evGeomCheck))) return rc;
+    {
+        int cus = 0;
+        if ((rc = cuCount(c, &cus))) return rc;
+        const unsigned blocks = (unsigned)(((size_t)N + kGeomCheckThreads - 1) / kGeomCheckThreads);
+        const unsigned grid = std::min(blocks, (unsigned)std::max(cus, 1) * 8u);
+        int *out = c->dGeomCheck.as<int>();
+        HIP_TRY(c, hipMemsetAsync(out, 0, sizeof(int) * checkInts, c->stream));
+        withBools([&](auto lds) {
+            hipLaunchKernelGGL(k_geom_check<lds.value>, dim3(grid), dim3(kGeomCheckThreads), 0, c->stream, d_vertices,
+                               (const int *)d_materialIds, N, numMaterials, out);
+        }, numMaterials <= kGeomCheckBins);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(c->hGeomCheck.p, out, sizeof(int) * checkInts, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipEventRecord(c->evGeomCheck, c->stream));
+        HIP_TRY(c, hipEventSynchronize(c->evGeomCheck));  // the call's only host wait apart from growth
+    }
+    const int *counts = c->hGeomCheck.as<int>();
+    if (counts[numMaterials]) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: a material id is outside [0, %d)", numMaterials);
+    if (counts[numMaterials + 1]) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: a vertex coordinate is not finite / exceeds 1e30");
+    long long lightSum = 0;
+    for (int m = 0; m < numMaterials; m++)
+        if (s.hostMats[(size_t)m].type == kMaterialLight) lightSum += counts[m];
+    const int numLights = (int)lightSum;
+    const int len = numLights + (s.ds.envTex >= 0 ? 1 : 0);
+
+    // 2. everything that can fail for want of memory, still before the scene is touched: events and pinned words, the builders' and
+    // the compaction's scratch, then the scene's own arrays (all fresh ones first, the old ones released only when every one is there)
+    if ((rc = len > 0 ? prepareLightSums(c) : ensureTreeHeader(c))) return rc;
+    BvhWork w{};
+    LbvhWork L{};
+    if ((rc = treeWorkspace(c, d_vertices, N, builder, L, w))) return rc;
+    EmitWork ew{};
+    if ((rc = growEmitWork(c, N, &ew))) return rc;
+    SceneRegrow g{c, {}, {}};
+    const bool growPrims = N > s.primCap, growLights = numLights > s.lightCap, growLen = len > s.lightLenCap;
+    auto allocate = [&]() -> int {
+        int e;
+        if (growPrims) {
+            const size_t cap = (size_t)N, capS = 2 * cap - 1;
+            if ((e = g.add(&s.ds.tris, sizeof(TriRec) * cap)) || (e = g.add(&s.ds.attrs, sizeof(AttrRec) * cap)) ||
+                (e = g.add(&s.ds.primClass, cap)) || (e = g.add(&s.ds.nodes[0], sizeof(NodeRec) * 6 * (capS + 1))) ||
+                (e = g.add(&s.updPairs, sizeof(PairRec) * ((capS - 1) / 2 + 1))))
+                return e;
+            if (s.prevTris && (e = g.add(&s.prevTris, sizeof(TriRec) * cap))) return e;
+        }
+        if (growLights)
+            if ((e = g.add(&s.ds.lights, sizeof(LightRec) * (size_t)numLights)) || (e = g.add(&s.ds.lightPre, sizeof(LightPre) * (size_t)numLights)) ||
+                (e = g.add(&s.dLightPrims, sizeof(int) * (size_t)numLights)))
+                return e;
+        if (growLen && (e = g.add(&s.ds.lightAlias, sizeof(AliasRec) * (size_t)len))) return e;
+        // the rebuild's scratch is laid out for the sampler's capacity: made here when the scene never had one, replaced when that grows
+        if (len > 0 && (growLen || !s.lightScratch) && (e = g.add(&s.lightScratch, aliasWorkBytes(std::max(len, s.lightLenCap))))) return e;
+        return RDH_OK;
+    };
+    if ((rc = allocate())) {
+        g.abandon();
+        return rc;
+    }
+    PairRec *pairs = nullptr;  // (growth: the fresh ones, below)
+    if (!growPrims && (rc = ensureUpdPairs(c, &pairs))) {
+        g.abandon();
+        return rc;
+    }
+    if (!g.fresh.empty()) {  // growth waits for everything that may still read the old arrays
+        hipError_t e = hipStreamSynchronize(c->stream);
+        for (hipStream_t side : {c->sideStream, c->litStream, c->wfStream})
+            if (side && e == hipSuccess) e = hipStreamSynchronize(side);
+        if (e != hipSuccess) {
+            g.abandon();
+            return fail(c, (int)e, "HIP error (%s:%d): hipStreamSynchronize: %s", __FILE__, __LINE__, hipGetErrorString(e));
+        }
+    }
+    if ((rc = dropObjects(c))) {  // the object table names triangles of the old set (an upload drops it too)
+        g.abandon();
+        return rc;
+    }
+    if (growPrims) {  // the upload's pairs go with the other arrays: from here on the tree's pairs are updPairs
+        const PairRec *uploaded = s.ds.pairs;
+        if (uploaded && uploaded != s.updPairs) sceneRelease(c, &uploaded, true);
+        s.ds.pairs = nullptr;  // until settleTree names the new ones
+    }
+    g.commit();
+    if (growPrims) s.primCap = N;
+    if (growLights) s.lightCap = numLights;
+    if (growLen) s.lightLenCap = len;
+    for (int k = 1; k < 6; k++) s.ds.nodes[k] = s.ds.nodes[0] + (size_t)k * ((size_t)S + 1);
+    if (growPrims) pairs = s.updPairs;
+
+    // 6. host state, set before the launches that are sized by it (everything below only enqueues)
+    s.ds.numPrims = N;
+    s.ds.bvhSize = S;
+    s.matPrims.assign(counts, counts + numMaterials);
+    s.planValid = false;
+    s.movedSinceRender = false;  // rdh_scene_track_motion: triangle p of the old set has no counterpart, "previous == current"
+    s.worldStale = false;
+    s.numLights = numLights;
+    s.ds.lightSamplerLength = len;  // at once, as after rdh_scene_set_materials
+
+    // 3. the records
+    if ((rc = waitSideStreams(c))) return rc;  // the arrays are rewritten in place
+    const unsigned primGrid = (unsigned)((N + 255) / 256);
+    hipLaunchKernelGGL(k_geom_pack, dim3(primGrid), dim3(256), 0, c->stream, d_vertices, d_normals, d_texcoords, (const int *)d_materialIds,
+                       s.ds.mats, N, const_cast<TriRec *>(s.ds.tris), const_cast<AttrRec *>(s.ds.attrs), const_cast<unsigned char *>(s.ds.primClass));
+    HIP_TRY(c, hipGetLastError());
+
+    // 4. the tree: rdh_scene_update_geometry's path at the new N and S
+    if ((rc = enqueueTree(c, builder, L, w, pairs))) return rc;
+
+    // 5. the lights, always: the ordered compaction over the scene's records, then what rdh_scene_rebuild_lights does
+    const SceneEmitters ld{s.ds.tris, s.ds.mats, const_cast<unsigned char *>(s.ds.primClass), s.dLightPrims, const_cast<LightRec *>(s.ds.lights),
+                           numLights};
+    hipLaunchKernelGGL(k_emit_count_scene, dim3(primGrid), dim3(256), 0, c->stream, ld, N, ew.blockTotals);
+    hipLaunchKernelGGL(k_emit_scan, dim3(1), dim3(256), 0, c->stream, ew.blockTotals, (int)primGrid, (const int *)nullptr, ew.total);
+    hipLaunchKernelGGL(k_emit_scatter_scene, dim3(primGrid), dim3(256), 0, c->stream, ld, N, (const int *)ew.blockTotals);
+    HIP_TRY(c, hipGetLastError());
+    s.listEdited = true;
+    if (len == 0) {  // nothing to sample: what an upload of a scene without lights holds; a rebuild still in flight is dropped
+        s.ds.sumLightPowerInv = 0.f;
+        s.lightsPending = false;
+        return RDH_OK;
+    }
+    return enqueueLightRebuild(c, envPower, nullptr);
+}
+
+long long rdh_debug_read_geometry(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
+    if (!c) return RDH_ERR_ARGS;
+    const SceneState &s = c->scene;
+    if (!s.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    const long long N = s.ds.numPrims;
+    long long bytes;
+    if (which == 0) bytes = (long long)sizeof(TriRec) * N;
+    else if (which == 1) bytes = (long long)sizeof(AttrRec) * N;
+    else if (which == 2) bytes = N;
+    else if (which == 3) bytes = (long long)(sizeof(int32_t) * s.matPrims.size());
+    else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_geometry: which = %d", which);
+    if (!hostOut) return bytes;
+    if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_geometry: %lld bytes needed", bytes);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (which == 0) HIP_TRY(c, hipMemcpy(hostOut, s.ds.tris, bytes, hipMemcpyDeviceToHost));
+    else if (which == 1) HIP_TRY(c, hipMemcpy(hostOut, s.ds.attrs, bytes, hipMemcpyDeviceToHost));
+    else if (which == 2) HIP_TRY(c, hipMemcpy(hostOut, s.ds.primClass, bytes, hipMemcpyDeviceToHost));
+    else memcpy(hostOut, s.matPrims.data(), (size_t)bytes);
     return bytes;
 }
 
