@@ -169,7 +169,13 @@ int rdh_scene_upload(rdh_ctx *ctx, const rdh_scene_desc *desc);
  * tree rdh_build_bvh makes of these vertices), its six threaded arrays, sibling pairs and root box, the emissive triangles' records
  * and their per-light constants.  Asynchronous on the context's stream (the next render call waits for the build before it
  * launches); restarts the persistent block order; ReSTIR reservoirs are kept.  Coordinates must be finite and below 1e30, as for
- * rdh_scene_upload (not checked here: that would need the vertices on the host). */
+ * rdh_scene_upload (not checked here: that would need the vertices on the host).  This is a precondition of the result, not a
+ * courtesy: the walkers test class-0 rays with a fast box test whose equality with the literal AABB::intersect rests on every
+ * t being finite, i.e. on |coord| < 1e30 (device/traverse.h: aabbFast).  The same holds for the _ex form, for
+ * rdh_scene_refit_geometry and for the world positions rdh_scene_pose_objects produces (X * rest pose): vertices outside the
+ * bound give undefined hits.  Texture coordinates must be finite and below 2^21 in magnitude (the procedural texture's cell
+ * index is int(uv * 1024), undefined beyond): the two entries that take them, rdh_scene_upload and rdh_scene_set_geometry,
+ * refuse others with RDH_ERR_ARGS. */
 typedef struct rdh_light_update {
     const void *lightSampler;   /* HOST BinomialDistrib<float>[lightSamplerLength], as in rdh_scene_desc              */
     int32_t lightSamplerLength; /* must equal the scene's current (rdh_scene_set_materials changes it)               */
@@ -275,7 +281,8 @@ long long rdh_debug_read_lights(rdh_ctx *ctx, int which, void *hostOut, long lon
  * RDH_ERR_ARGS.  count == 0: RDH_OK, nothing enqueued.  Objects not listed keep what the world arrays hold.  When the tree step
  * refuses (a refit's RDH_ERR_STATE) the records are unchanged and the world arrays are seeded from them again before the next
  * pose; the same happens after the caller's own rdh_scene_update_geometry[_ex] / rdh_scene_refit_geometry, so a pose after those
- * moves the listed objects and leaves the caller's vertices everywhere else.
+ * moves the listed objects and leaves the caller's vertices everywhere else.  The posed world positions must satisfy the upload's
+ * |coord| < 1e30 (see rdh_scene_update_geometry); the pose does not check it.
  * rdh_debug_read_world: test access to the world arrays (HOST float[9*numPrims] each).  Blocking. */
 typedef struct rdh_object_range { int32_t firstPrim, numPrims, restFirstPrim; } rdh_object_range;
 #define RDH_POSE_REFIT 0
@@ -360,7 +367,8 @@ long long rdh_debug_read_textures(rdh_ctx *ctx, int which, void *hostOut, long l
  * emissive-triangle list, LightRec, LightPre, alias table, lightSamplerLength and sumLightPowerInv.  With RDH_BVH_LBVH it is what
  * that upload followed by rdh_scene_update_geometry_ex(..., RDH_BVH_LBVH) on the same vertices holds.
  * One call: (1) one kernel over the caller's arrays counts the triangles of every material and flags a material id outside
- * [0, numMaterials) and a coordinate that fails the upload's fabs(x) < 1e30f; the call waits for these 4 * (numMaterials + 2) bytes
+ * [0, numMaterials), a coordinate that fails the upload's fabs(x) < 1e30f and a texture coordinate that fails its
+ * fabs(t) < 2^21; the call waits for these 4 * (numMaterials + 2) bytes
  * through pinned memory, its only host wait apart from growth, and a raised flag returns RDH_ERR_ARGS with the scene unchanged.
  * (2) A count above what the scene's arrays hold (triangles, emitters, sampler entries: each tracked on its own) allocates the new
  * arrays first and releases the old ones then, so a failed allocation leaves the scene as it was; growth waits for the stream and

@@ -1246,6 +1246,11 @@ static uint32_t displayByte(float c) {
 static float displayFilmic1(float c) {  // mathUtil.h:110-113
     return (c * (c * 0.22f + 0.03f) + 0.002f) / (c * (c * 0.22f + 0.3f) + 0.06f) - 1.f / 30.f;
 }
+static void displayFilmic(float *c) {  // Math::filmic (mathUtil.h:114-116), in place on c[3]
+    float d = displayFilmic1(11.2f);
+    for (int k = 0; k < 3; k++) c[k] = displayFilmic1(c[k] * 1.6f) / d;
+}
+static float displayAces1(float c) { return (c * (2.51f * c + 0.03f)) / (c * (2.43f * c + 0.59f) + 0.14f); }  // Math::ACES (:118-121)
 void orc_copy_image_to_pbo(uint8_t *pbo, const void *image, int width, int height, int kind, int toneMapping, float scale) {
     const long long n = (long long)width * height;
     for (long long idx = 0; idx < n; idx++) {
@@ -1253,11 +1258,10 @@ void orc_copy_image_to_pbo(uint8_t *pbo, const void *image, int width, int heigh
         if (kind == 0) {
             const float *img = (const float *)image;
             for (int k = 0; k < 3; k++) c[k] = img[3 * idx + k] * scale;
-            if (toneMapping == 1) {  // Math::filmic (mathUtil.h:114-116)
-                float d = displayFilmic1(11.2f);
-                for (int k = 0; k < 3; k++) c[k] = displayFilmic1(c[k] * 1.6f) / d;
+            if (toneMapping == 1) {
+                displayFilmic(c);
             } else if (toneMapping == 2) {  // Math::ACES (mathUtil.h:118-121)
-                for (int k = 0; k < 3; k++) c[k] = (c[k] * (2.51f * c[k] + 0.03f)) / (c[k] * (2.43f * c[k] + 0.59f) + 0.14f);
+                for (int k = 0; k < 3; k++) c[k] = displayAces1(c[k]);
             }
         } else if (kind == 1) {
             const float *img = (const float *)image;
@@ -1522,5 +1526,126 @@ float orc_reservoir_W(const void *r36, const void *material44, const float *n3, 
     return resvW(r, isec, m);
 }
 float orc_power_heuristic(float f, float g) { return powerHeuristic(f, g); }
+
+// ---- batch entries: loops over the hooks above, with the record layouts of tests/probe/device_probe.hip -------------------
+// (one ctypes call per input costs ~3 us; these make millions of inputs per test affordable).  No arithmetic lives here.
+void orc_aabb_intersect_n(const float *in12, int64_t n, int32_t *hit, float *tMin) {  // in: box6, ray6
+    for (int64_t i = 0; i < n; i++) hit[i] = orc_aabb_intersect(in12 + 12 * i, in12 + 12 * i + 6, tMin + i);
+}
+void orc_intersect_triangle_n(const float *in15, int64_t n, float *out4) {  // in: ray6, v9; out: hit (int bits), bary2, dist
+    for (int64_t i = 0; i < n; i++) {
+        int32_t h = orc_intersect_triangle(in15 + 15 * i, in15 + 15 * i + 6, out4 + 4 * i + 1, out4 + 4 * i + 3);
+        memcpy(out4 + 4 * i, &h, 4);
+    }
+}
+void orc_ray_n(const float *in6, int64_t n, float *out8) {  // getMTBVHId(dir), getMTBVHId(-dir), makeOffsetedRay(pos, dir)
+    for (int64_t i = 0; i < n; i++) {
+        const float *p = in6 + 6 * i;
+        vec3 pos(p[0], p[1], p[2]), dir(p[3], p[4], p[5]);
+        int32_t a = SceneView::getMTBVHId(dir), b = SceneView::getMTBVHId(-dir);
+        Ray r = makeOffsetedRay(pos, dir);
+        float *o = out8 + 8 * i;
+        memcpy(o, &a, 4);
+        memcpy(o + 1, &b, 4);
+        o[2] = r.origin.x; o[3] = r.origin.y; o[4] = r.origin.z;
+        o[5] = r.direction.x; o[6] = r.direction.y; o[7] = r.direction.z;
+    }
+}
+void orc_utilhash_n(const uint32_t *in, int64_t n, uint32_t *out) {
+    for (int64_t i = 0; i < n; i++) out[i] = utilhash(in[i]);
+}
+void orc_sincos_n(const float *in, int64_t n, float *out2) {
+    for (int64_t i = 0; i < n; i++) sincos_det(in[i], out2 + 2 * i, out2 + 2 * i + 1);
+}
+void orc_atan2_n(const float *in2, int64_t n, float *out) {
+    for (int64_t i = 0; i < n; i++) out[i] = atan2_det(in2[2 * i], in2[2 * i + 1]);
+}
+void orc_to_sphere_n(const float *in2, int64_t n, float *out3) {
+    for (int64_t i = 0; i < n; i++) {
+        vec3 v = toSphere(vec2(in2[2 * i], in2[2 * i + 1]));
+        out3[3 * i] = v.x; out3[3 * i + 1] = v.y; out3[3 * i + 2] = v.z;
+    }
+}
+void orc_to_plane_n(const float *in3, int64_t n, float *out2) {
+    for (int64_t i = 0; i < n; i++) {
+        vec2 v = toPlane(vec3(in3[3 * i], in3[3 * i + 1], in3[3 * i + 2]));
+        out2[2 * i] = v.x; out2[2 * i + 1] = v.y;
+    }
+}
+void orc_power_heuristic_n(const float *in2, int64_t n, float *out) {
+    for (int64_t i = 0; i < n; i++) out[i] = powerHeuristic(in2[2 * i], in2[2 * i + 1]);
+}
+// in 20 words: type, baseColor3, metallic, roughness, ior, n3, wo3, wi3, r3, unused; out 12: BSDF3, pdf, sample {dir3, bsdf3, pdf, type}
+void orc_material_n(const float *in20, int64_t n, float *out12) {
+    for (int64_t i = 0; i < n; i++) {
+        const float *p = in20 + 20 * i;
+        unsigned char m[44];  // the 44-byte Material: type .. ior from the record, the four map ids = none
+        const int32_t noMaps[4] = {NullTextureId, NullTextureId, NullTextureId, NullTextureId};
+        memcpy(m, p, 28);
+        memcpy(m + 28, noMaps, 16);
+        float o8[8], *o = out12 + 12 * i;
+        orc_material_eval(m, 0, p + 7, p + 10, p + 13, o8);
+        o[0] = o8[0]; o[1] = o8[1]; o[2] = o8[2];
+        orc_material_eval(m, 1, p + 7, p + 10, p + 13, o8);
+        o[3] = o8[0];
+        orc_material_eval(m, 2, p + 7, p + 10, p + 16, o + 4);
+    }
+}
+void orc_procedural_texture_n(const float *in2, int64_t n, float *out3) {
+    for (int64_t i = 0; i < n; i++) {
+        vec3 c = proceduralTexture(vec2(in2[2 * i], in2[2 * i + 1]));
+        out3[3 * i] = c.x; out3[3 * i + 1] = c.y; out3[3 * i + 2] = c.z;
+    }
+}
+void orc_linear_sample_n(const float *texels, int width, int height, const float *uv2, int64_t n, float *out3) {  // finite uv only
+    for (int64_t i = 0; i < n; i++) {
+        vec3 c = linearSample((const vec3 *)texels, vec2(uv2[2 * i], uv2[2 * i + 1]), width, height);
+        out3[3 * i] = c.x; out3[3 * i + 1] = c.y; out3[3 * i + 2] = c.z;
+    }
+}
+void orc_pow_gamma_n(const float *in, int64_t n, float *out) {
+    for (int64_t i = 0; i < n; i++) out[i] = om::pow_gamma_det(in[i]);
+}
+void orc_tonemap_n(const float *in3, int64_t n, float *out6) {  // filmic3, ACES3
+    for (int64_t i = 0; i < n; i++) {
+        float *o = out6 + 6 * i;
+        for (int k = 0; k < 3; k++) o[k] = in3[3 * i + k];
+        displayFilmic(o);
+        for (int k = 0; k < 3; k++) o[3 + k] = displayAces1(in3[3 * i + k]);
+    }
+}
+void orc_exp_pow_n(const float *in2, int64_t n, float *out3) {  // exp(x), exp(y), pow(x, y)
+    for (int64_t i = 0; i < n; i++) {
+        out3[3 * i] = om::exp_det(in2[2 * i]);
+        out3[3 * i + 1] = om::exp_det(in2[2 * i + 1]);
+        out3[3 * i + 2] = om::pow_det(in2[2 * i], in2[2 * i + 1]);
+    }
+}
+// in 20 words: r (9), rhs (9), rnd, M (int bits); out 45: r after op 2, 3, 0, 1, 4 of orc_reservoir_op
+void orc_reservoir_n(const float *in20, int64_t n, float *out45) {
+    static const int ops[5] = {2, 3, 0, 1, 4};
+    for (int64_t i = 0; i < n; i++) {
+        const float *p = in20 + 20 * i;
+        int32_t M;
+        memcpy(&M, p + 19, 4);
+        for (int k = 0; k < 5; k++) {
+            float *o = out45 + 45 * i + 9 * k;
+            memcpy(o, p, 36);
+            orc_reservoir_op(ops[k], o, p + 9, p[18], M);
+        }
+    }
+}
+
+// in 24 words: reservoir (9), type, baseColor3, metallic, roughness, ior, n3, wo3, 2 unused; out: orc_reservoir_W
+void orc_reservoir_w_n(const float *in24, int64_t n, float *out) {
+    for (int64_t i = 0; i < n; i++) {
+        const float *p = in24 + 24 * i;
+        unsigned char m[44];
+        const int32_t noMaps[4] = {NullTextureId, NullTextureId, NullTextureId, NullTextureId};
+        memcpy(m, p + 9, 28);
+        memcpy(m + 28, noMaps, 16);
+        out[i] = orc_reservoir_W(p, m, p + 16, p + 19);
+    }
+}
 
 }  // extern "C"

@@ -149,6 +149,29 @@ void orc_reservoir_op(int op, void *r36, const void *rhs36, float rnd, int M);
 float orc_reservoir_W(const void *r36, const void *material44, const float *n3, const float *wo3);
 float orc_power_heuristic(float f, float g); /* Math::powerHeuristic (mathUtil.h:81-84) */
 
+/* Batch entries: loops over the hooks above on n fixed-size records of 32-bit words, laid out as in
+ * tests/probe/device_probe.hip (the device-side probe of the same functions), plus thin exports of toSphere / toPlane
+ * (mathUtil.h:138-147), getMTBVHId (scene.h:114-129), makeOffsetedRay (intersections.h:16-18), proceduralTexture
+ * (scene.h:77-86), linearSample (image.h:42-87) and the tone-map curves (mathUtil.h:110-121).  No arithmetic of their own. */
+void orc_aabb_intersect_n(const float *in12, int64_t n, int32_t *hit, float *tMin);
+void orc_intersect_triangle_n(const float *in15, int64_t n, float *out4);
+void orc_ray_n(const float *in6, int64_t n, float *out8);
+void orc_utilhash_n(const uint32_t *in, int64_t n, uint32_t *out);
+void orc_sincos_n(const float *in, int64_t n, float *out2);
+void orc_atan2_n(const float *in2, int64_t n, float *out);
+void orc_to_sphere_n(const float *in2, int64_t n, float *out3);
+void orc_to_plane_n(const float *in3, int64_t n, float *out2);
+void orc_power_heuristic_n(const float *in2, int64_t n, float *out);
+void orc_material_n(const float *in20, int64_t n, float *out12);
+void orc_procedural_texture_n(const float *in2, int64_t n, float *out3);
+/* uv must be finite: linearSample's texel index is an out-of-range float -> int conversion otherwise. */
+void orc_linear_sample_n(const float *texels, int width, int height, const float *uv2, int64_t n, float *out3);
+void orc_pow_gamma_n(const float *in, int64_t n, float *out);
+void orc_tonemap_n(const float *in3, int64_t n, float *out6);
+void orc_exp_pow_n(const float *in2, int64_t n, float *out3);
+void orc_reservoir_n(const float *in20, int64_t n, float *out45);
+void orc_reservoir_w_n(const float *in24, int64_t n, float *out);
+
 #ifdef __cplusplus
 }
 #endif

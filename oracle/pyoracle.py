@@ -105,6 +105,12 @@ def lib():
                    "orc_trace_occluded", "orc_path_trace", "orc_path_trace_direct", "orc_gbuffer_render",
                    "orc_restir_direct", "orc_sincos", "orc_material_eval", "orc_camera_sample"):
             getattr(l, fn).restype = None
+        for fn in ("orc_intersect_triangle_n", "orc_ray_n", "orc_utilhash_n", "orc_sincos_n", "orc_atan2_n", "orc_to_sphere_n",
+                   "orc_to_plane_n", "orc_power_heuristic_n", "orc_material_n", "orc_procedural_texture_n", "orc_pow_gamma_n",
+                   "orc_tonemap_n", "orc_exp_pow_n", "orc_reservoir_n", "orc_reservoir_w_n"):
+            getattr(l, fn).argtypes, getattr(l, fn).restype = [vp, i64, vp], None
+        l.orc_aabb_intersect_n.argtypes, l.orc_aabb_intersect_n.restype = [vp, i64, vp, vp], None
+        l.orc_linear_sample_n.argtypes, l.orc_linear_sample_n.restype = [vp, i32, i32, vp, i64, vp], None
         _lib = l
     return _lib
 
@@ -325,3 +331,38 @@ def reservoir_W(r, material, n, wo):
 
 def power_heuristic(f, g):
     return float(lib().orc_power_heuristic(float(f), float(g)))
+
+
+# ---- batch entries (orc_*_n): n records of 32-bit words in, n records out, laid out as in tests/probe/device_probe.hip ----
+BATCH_WORDS = {  # name -> (words per input record, words per output record)
+    "intersect_triangle": (15, 4), "ray": (6, 8), "utilhash": (1, 1), "sincos": (1, 2), "atan2": (2, 1), "to_sphere": (2, 3),
+    "to_plane": (3, 2), "power_heuristic": (2, 1), "material": (20, 12), "procedural_texture": (2, 3), "pow_gamma": (1, 1),
+    "tonemap": (3, 6), "exp_pow": (2, 3), "reservoir": (20, 45), "reservoir_w": (24, 1),
+}
+
+
+def batch(name, records):
+    """orc_<name>_n over `records` (uint32 [n, words in]) -> uint32 [n, words out]."""
+    wi, wo = BATCH_WORDS[name]
+    rec = np.ascontiguousarray(records).view(np.uint32).reshape(-1, wi)
+    out = np.zeros((len(rec), wo), np.uint32)
+    getattr(lib(), f"orc_{name}_n")(rec.ctypes.data, len(rec), out.ctypes.data)
+    return out
+
+
+def aabb_intersect_n(records):
+    """orc_aabb_intersect over float32 [n, 12] = box6, ray6 -> (hit int32 [n], tMin float32 [n])."""
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, 12)
+    hit, t = np.zeros(len(rec), np.int32), np.zeros(len(rec), np.float32)
+    lib().orc_aabb_intersect_n(rec.ctypes.data, len(rec), hit.ctypes.data, t.ctypes.data)
+    return hit, t
+
+
+def linear_sample_n(texels, uv):
+    """linearSample of float32 texels [height, width, 3] at FINITE uv float32 [n, 2] -> float32 [n, 3]."""
+    tex = np.ascontiguousarray(texels, np.float32)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    assert np.isfinite(uv).all(), "linearSample's texel index is undefined (out of bounds on the host) for a non-finite uv"
+    out = np.zeros((len(uv), 3), np.float32)
+    lib().orc_linear_sample_n(tex.ctypes.data, tex.shape[1], tex.shape[0], uv.ctypes.data, len(uv), out.ctypes.data)
+    return out

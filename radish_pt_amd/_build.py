@@ -14,7 +14,7 @@ HOST_SOURCES = [os.path.join(CSRC, "host", "scene_build.cpp"), os.path.join(CSRC
 HIP_SOURCES = [os.path.join(CSRC, "radish_hip.hip")]
 HIP_DEPS = [
     os.path.join(CSRC, "device", f)
-    for f in ("rmath.h", "layouts.h", "traverse.h", "bsdf.h", "lights.h", "path_step.h", "kernels_pt.h", "kernels_restir.h", "kernels_wave.h", "kernels_persist.h", "kernels_walk.h", "wg_trace.h", "kernels_display.h", "kernels_denoise.h", "kernels_bvh.h", "kernels_refit.h", "kernels_lbvh.h", "kernels_lights.h", "kernels_pose.h", "kernels_materials.h", "kernels_textures.h")
+    for f in ("rmath.h", "layouts.h", "traverse.h", "bsdf.h", "lights.h", "path_step.h", "kernels_pt.h", "kernels_restir.h", "kernels_wave.h", "kernels_persist.h", "kernels_walk.h", "wg_trace.h", "kernels_display.h", "kernels_denoise.h", "kernels_bvh.h", "kernels_refit.h", "kernels_lbvh.h", "kernels_lights.h", "kernels_pose.h", "kernels_materials.h", "kernels_textures.h", "display_math.h", "denoise_math.h", "reservoir.h")
 ] + [os.path.join(ROOT, "include", "radish_hip.h")]
 
 # -ffp-contract=off: the HIP path must execute the same IEEE-754 operation sequence as the CPU checker
@@ -64,9 +64,25 @@ def build_variant(name, defines):
     return out
 
 
+PROBE_SOURCE = os.path.join(ROOT, "tests", "probe", "device_probe.hip")
+
+
+def build_probe(force=False, extra_flags=(), out=None):
+    """Test-only: tests/probe/libradish_probe.so, one tiny kernel around each __device__ function of the kernel-free headers,
+    compiled with exactly the product's HIP_FLAGS (plus hidden visibility: only the probe_* entries are exported).  The product
+    never loads it.  `extra_flags` / `out` are for scratch builds that show the tests can fail (select with RADISH_PROBE_LIB)."""
+    out = out or os.path.join(ROOT, "tests", "probe", "libradish_probe.so")
+    vmap = os.path.join(os.path.dirname(PROBE_SOURCE), "probe.map")  # linker script: hides the compiler's own __hip_cuid_* symbol too
+    if force or _newer(out, [PROBE_SOURCE, vmap] + HIP_DEPS):
+        _run([HIPCC] + HIP_FLAGS + ["-fvisibility=hidden"] + list(extra_flags) + ["-I", os.path.join(CSRC, "device"), "-o", out,
+              PROBE_SOURCE, "-Wl,-rpath,/opt/rocm/lib", "-Wl,--version-script=" + vmap])
+    return out
+
+
 def build_all(force=False):
     build_host(force)
     build_hip(force)
+    build_probe(force)
 
 
 if __name__ == "__main__":

@@ -19,21 +19,25 @@ namespace rd {
 
 constexpr int kGeomCheckBins = 1024;   // materials whose counts a workgroup keeps in LDS
 constexpr int kGeomCheckThreads = 256;
+constexpr float kTexcoordLimit = 2097152.f;  // 2^21; rdh_scene_upload applies the same test on the host
 
 // out[0 .. numMaterials): triangles per material (added to: the caller clears them); out[numMaterials]: 1 when an id is out of range
-// (such a triangle is counted nowhere); out[numMaterials + 1]: 1 when a coordinate is not finite or not below 1e30 in magnitude.
+// (such a triangle is counted nowhere); out[numMaterials + 1]: bit 0 when a vertex coordinate is not finite or not below 1e30 in
+// magnitude, bit 1 when a texture coordinate is not finite or not below 2^21 (kTexcoordLimit: int(uv * 1024) in proceduralTexture
+// must stay a defined conversion).
 // Grid-stride over the triangles, so a workgroup's bins serve many of them.  LDS: up to kGeomCheckBins materials the counts are
 // collected with integer LDS atomics and leave with one global atomic per non-empty bin and workgroup; beyond that every triangle
 // adds to its global counter.  The flags are OR-ed, one atomic per wave that saw one.
 template <bool LDS>
-__global__ __launch_bounds__(kGeomCheckThreads) void k_geom_check(const float *__restrict__ verts, const int *__restrict__ materialIds,
-                                                                 int numPrims, int numMaterials, int *__restrict__ out) {
+__global__ __launch_bounds__(kGeomCheckThreads) void k_geom_check(const float *__restrict__ verts, const float *__restrict__ texcoords,
+                                                                 const int *__restrict__ materialIds, int numPrims, int numMaterials,
+                                                                 int *__restrict__ out) {
     __shared__ int bins[LDS ? kGeomCheckBins : 1];
     if (LDS) {
         for (int m = (int)threadIdx.x; m < numMaterials; m += kGeomCheckThreads) bins[m] = 0;
         __syncthreads();
     }
-    bool badId = false, badCoord = false;
+    bool badId = false, badCoord = false, badTex = false;
     const long long stride = (long long)gridDim.x * kGeomCheckThreads;
     for (long long p = (long long)blockIdx.x * kGeomCheckThreads + threadIdx.x; p < numPrims; p += stride) {
         const int id = materialIds[p];
@@ -45,11 +49,18 @@ __global__ __launch_bounds__(kGeomCheckThreads) void k_geom_check(const float *_
 #pragma unroll
         for (int k = 0; k < 9; k++) ok = ok && (__builtin_fabsf(v[k]) < 1e30f);  // false for NaN, as the upload's test
         badCoord = badCoord || !ok;
+        const float *t = texcoords + 6 * (size_t)p;
+        ok = true;
+#pragma unroll
+        for (int k = 0; k < 6; k++) ok = ok && (__builtin_fabsf(t[k]) < kTexcoordLimit);
+        badTex = badTex || !ok;
     }
     const bool anyId = __ballot(badId) != 0ull, anyCoord = __ballot(badCoord) != 0ull;  // (every lane of the wave is here)
+    const bool anyTex = __ballot(badTex) != 0ull;
     if ((threadIdx.x & 63) == 0) {
         if (anyId) atomicOr(&out[numMaterials], 1);
         if (anyCoord) atomicOr(&out[numMaterials + 1], 1);
+        if (anyTex) atomicOr(&out[numMaterials + 1], 2);
     }
     if (LDS) {
         __syncthreads();

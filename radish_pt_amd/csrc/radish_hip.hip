@@ -1181,6 +1181,8 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
         const float *t = d->texcoords + 6 * (size_t)p;
         int mid = d->materialIds[p];
         if (mid < 0 || mid >= d->numMaterials) return fail(c, RDH_ERR_ARGS, "materialIds[%d] = %d out of range", p, mid);
+        for (int q = 0; q < 6; q++)  // int(uv * 1024) in proceduralTexture must stay a defined conversion
+            if (!(std::fabs(t[q]) < kTexcoordLimit)) return fail(c, RDH_ERR_ARGS, "texcoords of triangle %d are not finite / reach 2^21", p);
         tris[p].a = make_float4(v[0], v[1], v[2], v[3]);
         tris[p].b = make_float4(v[4], v[5], v[6], v[7]);
         tris[p].c = make_float4(v[8], asFloat(mid), 0.f, 0.f);
@@ -3662,7 +3664,7 @@ int rdh_scene_set_geometry(rdh_ctx *c, const float *d_vertices, const float *d_n
         int *out = c->dGeomCheck.as<int>();
         HIP_TRY(c, hipMemsetAsync(out, 0, sizeof(int) * checkInts, c->stream));
         withBools([&](auto lds) {
-            hipLaunchKernelGGL(k_geom_check<lds.value>, dim3(grid), dim3(kGeomCheckThreads), 0, c->stream, d_vertices,
+            hipLaunchKernelGGL(k_geom_check<lds.value>, dim3(grid), dim3(kGeomCheckThreads), 0, c->stream, d_vertices, d_texcoords,
                                (const int *)d_materialIds, N, numMaterials, out);
         }, numMaterials <= kGeomCheckBins);
         HIP_TRY(c, hipGetLastError());
@@ -3672,7 +3674,8 @@ int rdh_scene_set_geometry(rdh_ctx *c, const float *d_vertices, const float *d_n
     }
     const int *counts = c->hGeomCheck.as<int>();
     if (counts[numMaterials]) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: a material id is outside [0, %d)", numMaterials);
-    if (counts[numMaterials + 1]) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: a vertex coordinate is not finite / exceeds 1e30");
+    if (counts[numMaterials + 1] & 1) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: a vertex coordinate is not finite / exceeds 1e30");
+    if (counts[numMaterials + 1] & 2) return fail(c, RDH_ERR_ARGS, "rdh_scene_set_geometry: a texture coordinate is not finite / reaches 2^21");
     long long lightSum = 0;
     for (int m = 0; m < numMaterials; m++)
         if (s.hostMats[(size_t)m].type == kMaterialLight) lightSum += counts[m];

@@ -94,8 +94,8 @@ def test_geometry_kernels_use_no_scratch():
         src = os.path.join(tmp, "geometry_only.hip")
         with open(src, "w") as f:
             f.write('#include "device/kernels_geometry.h"\n'
-                    "template __global__ void rd::k_geom_check<true>(const float *, const int *, int, int, int *);\n"
-                    "template __global__ void rd::k_geom_check<false>(const float *, const int *, int, int, int *);\n")
+                    "template __global__ void rd::k_geom_check<true>(const float *, const float *, const int *, int, int, int *);\n"
+                    "template __global__ void rd::k_geom_check<false>(const float *, const float *, const int *, int, int, int *);\n")
         cmd = [HIPCC] + flags + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "radish_pt_amd", "csrc"), "-c", src,
                                  "-o", os.path.join(tmp, "x.o"), "-Rpass-analysis=kernel-resource-usage"]
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)

@@ -558,3 +558,34 @@ def test_refusals_leave_the_scene_unchanged(make_ctx, uploaded):
     # the error flags do not stick: the same arrays, unbroken, go through
     assert raw() == 0
     _assert_same_state(_state(ctx), _state(make_ctx(ed, cam)), "after the accepted call")
+
+
+def test_texcoords_beyond_the_bound_are_refused(make_ctx):
+    """proceduralTexture's cell index is int(uv * 1024): from |uv| = 2^21 on that conversion is undefined (and differs between the
+    host checker and gfx950), so both entries that take texture coordinates refuse them, and what they accept stays usable."""
+    from radish_pt_amd import api
+
+    lib = api.lib()
+    sd, cam = geometry_edit.SCENES["cornell"](), _cam("cornell")
+    ctx = make_ctx(sd, cam)
+    v, nr, t, m = (_cuda(a) for a in geometry_edit.arrays(sd))
+    n = sd.num_prims
+    ptr = lambda x: C.c_void_p(x.data_ptr())
+    state = _state(ctx)
+    for where in (0, 3 * n + 1, 6 * n - 1):
+        for bad in (2.0 ** 21, -(2.0 ** 21), float("nan"), float("inf")):
+            broken = t.clone()
+            broken[where] = bad
+            assert lib.rdh_scene_set_geometry(ctx.h, ptr(v), ptr(nr), ptr(broken), ptr(m), n, api.RDH_BVH_SAH, float(sd.env_power)) == -1
+            assert b"texture coordinate" in lib.rdh_last_error(ctx.h)
+    _assert_same_state(_state(ctx), state, "after the refused texcoords")
+    edge = t.clone()
+    edge[0] = float(np.nextafter(np.float32(2.0 ** 21), np.float32(0)))  # the largest accepted value
+    ctx.set_geometry(v, nr, edge, m, env_power=float(sd.env_power))
+    import copy
+
+    bad_sd = copy.copy(sd)
+    bad_sd.texcoords = sd.texcoords.copy()
+    bad_sd.texcoords.reshape(-1)[5] = 2.0 ** 21
+    with pytest.raises(api.RadishError, match="texcoords"):
+        make_ctx(bad_sd, cam)

@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+from float64_models import linear_sample_py as _linear_sample_py, metallic_ref as _metallic_ref, norm as _norm, utilhash_py as _utilhash_py
 from helpers import random_rays, random_segments
 
 
@@ -23,17 +24,6 @@ def _f(x):
 # ---------------------------------------------------------------------------------------------------------------------
 # utilhash (src/mathUtil.h:199-207) against Python big-int arithmetic
 # ---------------------------------------------------------------------------------------------------------------------
-def _utilhash_py(a):
-    M = 0xFFFFFFFF
-    a = ((a + 0x7ED55D16) + (a << 12)) & M
-    a = ((a ^ 0xC761C23C) ^ (a >> 19)) & M
-    a = ((a + 0x165667B1) + (a << 5)) & M
-    a = ((a + 0xD3A2646C) ^ (a << 9)) & M
-    a = ((a + 0xFD7046C5) + (a << 3)) & M
-    a = ((a ^ 0xB55A4F09) ^ (a >> 16)) & M
-    return a
-
-
 def test_utilhash_vectors():
     lib = _lib()
     for a in [0, 1, 2, 63, 64, 1919, 2073599, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF, 123456789]:
@@ -196,37 +186,6 @@ def _mat_eval(mat, which, n, wo, w):
     n32, wo32, w32 = (np.ascontiguousarray(a, np.float32) for a in (n, wo, w))  # keep alive across the call
     _lib().orc_material_eval(buf.ctypes.data, which, n32.ctypes.data, wo32.ctypes.data, w32.ctypes.data, out.ctypes.data)
     return out
-
-
-def _norm(v):
-    v = np.asarray(v, np.float64)
-    return v / np.linalg.norm(v)
-
-
-def _metallic_ref(base, metallic, rough, n, wo, wi):
-    alpha = rough * rough
-    h = _norm(wo + wi)
-    cosO, cosI = n @ wo, n @ wi
-    if cosI * cosO < 1e-7:
-        return np.zeros(3), None
-    f0 = 0.08 * (1 - metallic) + base * metallic
-    f = f0 + (1 - f0) * (1 - h @ wo) ** 5
-    def ggxD(c):
-        if c < 1e-6:
-            return 0.0
-        a2 = alpha * alpha
-        return a2 / (math.pi * ((c * c) * (a2 - 1) + 1) ** 2)
-    def schlickG(c):
-        a = alpha * 0.5
-        return c / (c * (1 - a) + a)
-    d = ggxD(n @ h)
-    g = schlickG(abs(cosO)) * schlickG(abs(cosI))
-    diffuse = base / math.pi * (1 - metallic)
-    bsdf = diffuse * (1 - f) + (g * d / (4 * cosI * cosO)) * f
-    pdf_spec = ggxD(n @ h) * schlickG(n @ wo) * abs(h @ wo) / abs(n @ wo) / (4 * abs(h @ wo))
-    pdf_diff = max(n @ wi, 0) / math.pi
-    a = 1 / (2 - metallic)
-    return bsdf, pdf_diff * (1 - a) + pdf_spec * a
 
 
 def test_bsdf_eval_vs_float64():
@@ -464,23 +423,6 @@ def _tex(o, tex_id, uv):
     uv32 = np.ascontiguousarray(uv, np.float32)
     _lib().orc_texture_sample(o.h, tex_id, uv32.ctypes.data, out.ctypes.data)
     return out
-
-
-def _linear_sample_py(t, u, v):
-    """float64 re-derivation of linearSample from the reference text (src/image.h:42-87)."""
-    h, w, _ = t.shape
-    fr = lambda x: x - math.floor(x)
-    u, v = fr(u), fr(v)
-    fx, fy = u * w + 0.5, v * h + 0.5
-    ix = int(fx if fr(fx) > 0.5 else fx - 1)
-    iy = int(fy if fr(fy) > 0.5 else fy - 1)
-    ix += w if ix < 0 else 0
-    iy += h if iy < 0 else 0
-    ux, uy = (ix + 1) % w, (iy + 1) % h
-    lx, ly = fr(fx + 0.5), fr(fy + 0.5)
-    c1 = t[iy, ix] * (1 - lx) + t[iy, ux] * lx
-    c2 = t[uy, ix] * (1 - lx) + t[uy, ux] * lx
-    return c1 * (1 - ly) + c2 * ly
 
 
 def test_linear_sample_known_answers():
