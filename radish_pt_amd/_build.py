@@ -79,10 +79,47 @@ def build_probe(force=False, extra_flags=(), out=None):
     return out
 
 
+SHIM_HEADER = os.path.join(CSRC, "radish_shim.hpp")
+SHIM_RUNNER_SOURCE = os.path.join(ROOT, "tests", "shim", "shim_runner.cpp")
+SHIM_RUNNER_FORMS = {  # binary name -> the shim's form
+    "shim_runner": [],
+    "shim_runner_multi_gpu": ["-DRADISH_SHIM_MULTI_GPU"],
+    "shim_runner_one_process": ["-DRADISH_SHIM_ONE_PROCESS_GPUS"],
+}
+
+
+def build_shim_runner(force=False, out_dir=None, shim=None):
+    """Test-only: tests/shim/shim_runner{,_multi_gpu,_one_process}, host-only programs (hipcc as C++, no device code) that run
+    radish_shim.hpp in its three forms against tests/shim/ref_decls.h, linked against libradish_hip.so (found through an
+    $ORIGIN-relative run path) and the HIP runtime.  The product never starts them.  `out_dir` / `shim` are for scratch builds
+    against a changed copy of the header (a file named radish_shim.hpp in another directory) that show the tests can fail
+    (select with RADISH_SHIM_RUNNER_DIR).  Returns the three paths."""
+    out_dir = os.path.abspath(out_dir or os.path.dirname(SHIM_RUNNER_SOURCE))
+    shim = os.path.abspath(shim or SHIM_HEADER)
+    if os.path.basename(shim) != "radish_shim.hpp":
+        raise ValueError("the runner includes \"radish_shim.hpp\": a changed copy keeps that name, in a directory of its own")
+    os.makedirs(out_dir, exist_ok=True)
+    deps = [SHIM_RUNNER_SOURCE, os.path.join(os.path.dirname(SHIM_RUNNER_SOURCE), "ref_decls.h"), shim,
+            os.path.join(ROOT, "include", "radish_hip.h")]
+    outs = []
+    for name, defines in SHIM_RUNNER_FORMS.items():
+        out = os.path.join(out_dir, name)
+        outs.append(out)
+        if force or _newer(out, deps):
+            if not os.path.exists(os.path.join(CSRC, "libradish_hip.so")):
+                build_hip()  # the link needs the library to exist, not to be current: its exports are fixed by include/radish_hip.h
+            _run([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-Wno-unused-function", "-D__HIP_PLATFORM_AMD__=1"]
+                 + defines + ["-I", os.path.dirname(shim), "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
+                              SHIM_RUNNER_SOURCE, "-o", out, "-L", CSRC, "-lradish_hip", "-L", "/opt/rocm/lib", "-lamdhip64", "-ldl",
+                              "-Wl,-rpath,$ORIGIN/" + os.path.relpath(CSRC, out_dir), "-Wl,-rpath,/opt/rocm/lib"])
+    return outs
+
+
 def build_all(force=False):
     build_host(force)
     build_hip(force)
     build_probe(force)
+    build_shim_runner(force)
 
 
 if __name__ == "__main__":

@@ -8,9 +8,12 @@
 // keeping the declarations in pathtrace.h / restir.h / gBuffer.h / scene.h untouched, so main.cpp and scene.cpp call
 // exactly what they call today.  It needs only what those translation units already include (glm, the reference's
 // own Scene / Camera / GBuffer / Settings / State definitions).  glm and the reference's headers are not available in the
-// build image, so it cannot be LINKED into Radish here; tests/test_shim_compiles.py compiles it
-// (-fsyntax-only, -Wall -Werror) against a minimal local set of the declarations it touches (tests/shim/), so that a typo
-// cannot ship, and the Python mirror radish_pt_amd/api.py is the host side the GPU tests exercise.
+// build image, so it has not been linked into Radish itself.  What runs: tests/shim/ref_decls.h declares, in a
+// minimal form with layout asserts, the reference types this header touches; tests/test_shim_compiles.py compiles the header
+// against it (-fsyntax-only, -Wall -Werror, all three forms), and tests/shim/shim_runner.cpp links the same pair against
+// libradish_hip.so and RUNS every function and class below on the GPU, in all three forms with one GPU, each result held to
+// the CPU oracle by bits (tests/test_gpu_shim_runs.py).  What does not: real glm and the real reference headers, and more
+// than one GPU.  (The Python mirror radish_pt_amd/api.py is the host side the other GPU tests and bench.py exercise.)
 //
 // Macros:  RADISH_SHIM_NO_REFERENCE_HEADERS  the including file has already declared glm / Camera / GBuffer / Scene /
 //                                            Settings / State (skip the reference's #includes)
