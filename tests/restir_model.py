@@ -16,7 +16,9 @@ The reference's kernel has a `__syncthreads()` between storing `reservoirTemp` a
 only one 8x8 block; the model follows the two-pass reading (every pixel's store before any pixel's spatial reuse).
 
 Geometry is restricted to horizontal quads (two triangles each, one authored normal per quad), so `_hit_quads` is the whole
-intersector; no environment map, no textures.  Draws rejected by `sampleDirectLightNoVisibility` leave Li, wi and dist at zero
+intersector; no environment map, no textures.  (That restriction is ModelScene's alone: the steps below reach geometry, materials
+and lights through the scene's methods only, and tests/path_model.py's PathScene answers them on general triangles with the
+surface fetch, the four maps and the environment map — tests/path_model_checks.py runs the same three steps on it.)  Draws rejected by `sampleDirectLightNoVisibility` leave Li, wi and dist at zero
 (the reference leaves them uninitialised; the project defines them).
 """
 import numpy as np
@@ -55,43 +57,67 @@ class ModelScene:
         self.mat_metallic = sd.materials["metallic"].astype(np.float64)
         self.mat_roughness = sd.materials["roughness"].astype(np.float64)
 
+    # What the three steps ask of a scene.  `handle` is whatever intersect() returned second, for all its rays; here the
+    # material ids.
+    def intersect(self, org, dirs):
+        """scene->intersect on quads: (hit, handle, pos, interpolated normal, material id)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t, q = _hit_quads(org, dirs, self.quads)
+        hit = q >= 0
+        qq = np.maximum(q, 0)
+        pos = org + dirs * np.where(hit, t, 0.0)[:, None]
+        return hit, self.quad_mat[qq], pos, self.quad_normal[qq], self.quad_mat[qq]
+
+    def occluded(self, x, y):
+        """testOcclusion(x, y) (scene.h:303-334): the segment shortened by 1e-4, its origin pushed 1e-5 along it."""
+        d = y - x
+        dist = np.linalg.norm(d, axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d = d / dist[:, None]
+            t, _ = _hit_quads(x + d * 1e-5, d, self.quads)
+        return t < dist - 1e-4  # a zero-length segment has a NaN direction and hits nothing
+
+    def bsdf(self, handle, rows, n, wo, wi):
+        """Material::BSDF with baseColor = 1 (restir.cu:125), rows of (n, wo, wi): Lambertian 1/pi, MetallicWorkflow by the
+        float64 statement of tests/test_oracle_kat.py, Dielectric 0 (material.h:131-134, 149-152, 187-204)."""
+        mat = handle[rows]
+        out = np.zeros((len(mat), 3))
+        ty = self.mat_type[mat]
+        out[ty == LAMBERTIAN] = 1.0 / PI
+        one = np.ones(3)
+        for k in np.flatnonzero(ty == METALLIC_WORKFLOW):
+            if not wi[k].any():
+                continue  # the zero sample of a rejected draw: cosI = 0 and the BSDF is 0
+            out[k] = _metallic_ref(one, self.mat_metallic[mat[k]], self.mat_roughness[mat[k]], n[k], wo[k], wi[k])[0]
+        return out
+
+    def sample_light_no_visibility(self, pos, r4):
+        """sampleDirectLightNoVisibility (scene.h:458-492): (pdf, radiance, wi, dist, accepted)."""
+        pdf, rad, wi, dist, _, valid = light_pdf_f64(self.sd, pos, r4)
+        return pdf, rad, wi, dist, valid
+
+    def albedo(self, handle):
+        return self.mat_color[handle]
+
+    def miss_colour(self, dirs):
+        """What a primary ray that hits nothing shows (restir.cu:117-122, gBuffer.cu:61-66): black without an environment map."""
+        return np.zeros((len(dirs), 3))
+
 
 def _dot(a, b):
     return np.einsum("...j,...j->...", a, b)
 
 
 def _intersect(scene, org, dirs):
-    """scene->intersect on quads: (hit, quad, pos, interpolated normal, material id)."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t, q = _hit_quads(org, dirs, scene.quads)
-    hit = q >= 0
-    qq = np.maximum(q, 0)
-    pos = org + dirs * np.where(hit, t, 0.0)[:, None]
-    return hit, qq, pos, scene.quad_normal[qq], scene.quad_mat[qq]
+    return scene.intersect(org, dirs)
 
 
 def _occluded(scene, x, y):
-    """testOcclusion(x, y) (scene.h:303-334): the segment shortened by 1e-4, its origin pushed 1e-5 along it."""
-    d = y - x
-    dist = np.linalg.norm(d, axis=1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        d = d / dist[:, None]
-        t, _ = _hit_quads(x + d * 1e-5, d, scene.quads)
-    return t < dist - 1e-4  # a zero-length segment has a NaN direction and hits nothing
+    return scene.occluded(x, y)
 
 
-def _bsdf(scene, mat, n, wo, wi):
-    """Material::BSDF with baseColor = 1 (restir.cu:125), rows of (n, wo, wi): Lambertian 1/pi, MetallicWorkflow by the float64
-    statement of tests/test_oracle_kat.py, Dielectric 0 (material.h:131-134, 149-152, 187-204)."""
-    out = np.zeros((len(mat), 3))
-    ty = scene.mat_type[mat]
-    out[ty == LAMBERTIAN] = 1.0 / PI
-    one = np.ones(3)
-    for k in np.flatnonzero(ty == METALLIC_WORKFLOW):
-        if not wi[k].any():
-            continue  # the zero sample of a rejected draw: cosI = 0 and the BSDF is 0
-        out[k] = _metallic_ref(one, scene.mat_metallic[mat[k]], scene.mat_roughness[mat[k]], n[k], wo[k], wi[k])[0]
-    return out
+def _bsdf(scene, handle, rows, n, wo, wi):
+    return scene.bsdf(handle, rows, n, wo, wi)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -187,12 +213,12 @@ def gbuffer(scene, cam, last_cam):
     W, H = (int(v) for v in cam["resolution"])
     n = W * H
     org, dirs = _camera_rays_f64(cam, W, H, np.full((n, 2), 0.5))
-    hit, _, pos, nrm, mat = _intersect(scene, org, dirs)
+    hit, handle, pos, nrm, mat = _intersect(scene, org, dirs)
     light = scene.mat_type[mat] == LIGHT
     rc = raster_coord(cam if last_cam is None else last_cam, np.where(hit[:, None], pos, org + dirs))
     inside = (rc[:, 0] >= 0) & (rc[:, 0] < W) & (rc[:, 1] >= 0) & (rc[:, 1] < H)
     return {
-        "albedo": np.where(hit[:, None], scene.mat_color[mat], 0.0),
+        "albedo": np.where(hit[:, None], scene.albedo(handle), scene.miss_colour(dirs)),  # :43-45, :61-66
         "normal": np.where(hit[:, None], nrm, 0.0),
         "primId": np.where(hit, np.where(light, NULL_PRIMITIVE - 1, mat), NULL_PRIMITIVE),
         "depth": np.where(hit, np.linalg.norm(pos - org, axis=1), 1.0),
@@ -260,7 +286,7 @@ def pass1(scene, cam, looper, gb_planes, last_reservoirs, first_frame, reuse, fa
     stored = status == 0
     return {"out": {k: full(v) for k, v in out.items()}, "temp": {k: full(v) for k, v in temp.items()}, "stored": stored,
             "stored_temp": stored & bool(reuse & SPATIAL), "dims": dims, "status": status, "pos": full(c["pos"]),
-            "normal": full(c["normal"]), "wo": full(c["wo"]), "mat": mat, "live": {k: full(v) for k, v in live.items()}}
+            "normal": full(c["normal"]), "wo": full(c["wo"]), "mat": mat, "handle": c["handle"], "miss_colour": c["miss_colour"], "live": {k: full(v) for k, v in live.items()}}
 
 
 _CANDIDATE_CACHE = {}
@@ -277,7 +303,7 @@ def _candidates(scene, cam, looper, faithful):
     idx = np.arange(n)
     u = sobol_draws(scene.sd.sobol, looper, idx, MAX_DIMS)
     org, dirs = _camera_rays_f64(cam, W, H, u[:, 0:2])  # sample4D: the lens draws .z, .w are unused by a pinhole
-    hit, _, pos, nrm, mat = _intersect(scene, org, dirs)
+    hit, handle, pos, nrm, mat = _intersect(scene, org, dirs)
     status = np.where(~hit, 1, np.where(scene.mat_type[mat] == LIGHT, 2, 0))  # :117-130
     sh = np.flatnonzero(status == 0)
     pos_s, mat_s, wo = pos[sh], mat[sh], -dirs[sh]
@@ -287,11 +313,11 @@ def _candidates(scene, cam, looper, faithful):
     r = empty_reservoirs(len(sh))
     for i in range(RESERVOIR_SIZE):  # :140-156
         c = 4 + 5 * i
-        pdf, rad, wi, dist, _, valid = light_pdf_f64(scene.sd, pos_s, u[sh, c:c + 4])
+        pdf, rad, wi, dist, valid = scene.sample_light_no_visibility(pos_s, u[sh, c:c + 4])
         Li = np.where(valid[:, None], rad, 0.0)
         wi = np.where(valid[:, None], wi, 0.0)
         dist = np.where(valid, dist, 0.0)
-        p_hat = Li * _bsdf(scene, mat_s, n_s, wo, wi) * np.maximum(_dot(n_s, wi), 0.0)[:, None]
+        p_hat = Li * _bsdf(scene, handle, sh, n_s, wo, wi) * np.maximum(_dot(n_s, wi), 0.0)[:, None]
         with np.errstate(divide="ignore", invalid="ignore"):
             w = np.linalg.norm(p_hat / pdf[:, None], axis=1)
         w = np.where(np.isnan(w) | np.isinf(w) | (pdf <= 0.0), 0.0, w)
@@ -308,7 +334,7 @@ def _candidates(scene, cam, looper, faithful):
         r["dist"] = np.where(take, dist, r["dist"])
     shadowed = _occluded(scene, pos_s, pos_s + r["wi"] * r["dist"][:, None])  # :158-163
     r["weight"] = np.where(shadowed, 0.0, r["weight"])
-    c = {"scene": scene, "u": u, "sh": sh, "status": status, "mat": mat, "reservoir": r, "pos": pos_s, "normal": n_s, "wo": wo, "flipped": flip,
+    c = {"scene": scene, "u": u, "sh": sh, "status": status, "mat": mat, "handle": handle, "miss_colour": scene.miss_colour(dirs), "reservoir": r, "pos": pos_s, "normal": n_s, "wo": wo, "flipped": flip,
          "shadowed": shadowed}
     _CANDIDATE_CACHE[key] = c
     return c
@@ -379,8 +405,9 @@ def pass2(scene, cam, looper, gb_planes, temp_reservoirs, pass1_state, reuse, it
         live.update({"final_skipped_own_invalid": _invalid(r) & ~final, "final_skipped_agg_invalid": _invalid(agg),
                      "final_merged": final, "first_spatial_dim": first_dim})
     direct = np.zeros((n, 3))
-    direct[st["status"] == 2] = 1.0  # an emitter seen directly: baseColor = 1 (:125-130); a miss without an env map: 0
-    p_hat = r["Li"] * _bsdf(scene, st["mat"][sh], st["normal"][sh], st["wo"][sh], r["wi"]) \
+    direct[st["status"] == 2] = 1.0  # an emitter seen directly: baseColor = 1 (:125-130)
+    direct[st["status"] == 1] = st["miss_colour"][st["status"] == 1]  # a miss: the map's colour, 0 without one (:117-122)
+    p_hat = r["Li"] * _bsdf(scene, st["handle"], sh, st["normal"][sh], st["wo"][sh], r["wi"]) \
         * np.maximum(_dot(st["normal"][sh], r["wi"]), 0.0)[:, None]
     with np.errstate(divide="ignore", invalid="ignore"):
         Wr = _f32_range(r["weight"] / (np.linalg.norm(p_hat, axis=1) * r["numSamples"]))  # Reservoir::W (restir.h:37-40)

@@ -153,8 +153,8 @@ def check_frame(ms, f, cams, reuse, faithful, t):
     reservoirs as RESERVOIR_DTYPE records) against the model's three steps.  Returns {step: excluded pixel indices}."""
     cam, last_cam = cams[f], (cams[f - 1] if f else None)
     ex = {}
-    tag = (f, reuse, faithful)
-    gb = _memo(("gb", f), (), lambda: M.gbuffer(ms, cam, last_cam))
+    tag = (f, reuse, faithful, id(ms))  # the scene too: tests/path_model_checks.py runs the same sequence on another one
+    gb = _memo(("gb", f, id(ms)), (), lambda: M.gbuffer(ms, cam, last_cam))
     ex["gbuffer"] = np.flatnonzero(gbuffer_bad(gb, t["planes"]))
     planes = planes_for_model(t["planes"], t["last_planes"])  # the tested code's planes from here on
 
@@ -191,10 +191,11 @@ def run_oracle(sd, cams, reuse, faithful):
     """The frames as check_frame reads them, from pyoracle's gbuffer_render and restir_direct."""
     from oracle import pyoracle
 
+    w, h = (int(v) for v in cams[0]["resolution"])
     o = pyoracle.OracleScene(sd)
-    gb = pyoracle.GBufferHost(W, H)
-    res = [np.zeros(N, L.RESERVOIR_DTYPE) for _ in range(3)]  # cur, last, temp (restir.cu:4-7)
-    img = np.zeros((N, 3), np.float32)
+    gb = pyoracle.GBufferHost(w, h)
+    res = [np.zeros(w * h, L.RESERVOIR_DTYPE) for _ in range(3)]  # cur, last, temp (restir.cu:4-7)
+    img = np.zeros((w * h, 3), np.float32)
     frames = []
     for f, cam in enumerate(cams):
         o.gbuffer_render(cam, gb)

@@ -62,12 +62,13 @@ def _run_gpu(ctx, setup, reuse, faithful, restir_flags, gbuffer_flags=0, restir=
 
     torch = _torch()
     cams = setup["cams"]
+    w, h = (int(v) for v in cams[0]["resolution"])  # tests/test_gpu_path_model.py drives its own scene and size through here
     ctx.set_partition(0, 1, 64)
     ctx.upload_scene(setup["sd"])
     ctx.set_camera(cams[0])
     gb = api.GBuffer()
-    gb.create(C.W, C.H)
-    img = torch.zeros(C.N, 3, device="cuda")
+    gb.create(w, h)
+    img = torch.zeros(w * h, 3, device="cuda")
     if restir:
         ctx.restir_init()
     frames = []

@@ -11,6 +11,9 @@ checked against the oracle:
     sampling, the emitter-hit MIS weight, HDRToLDR                                       (src/pathtrace.cu:149-291)
   * statistics: the mean of 256 frames of two-pass ReSTIR (corrected RIS) against a brute-force quadrature over all lights of
     the integral the reference's estimator defines                                       (src/restir.cu:97-203)
+These use horizontal Lambertian quads with one authored normal each, zero texcoords, no textures and no environment map; what a
+general triangle, a texture, the environment map, glass or metal adds to the path is stated in tests/path_model.py and checked by
+tests/test_path_model_cpu.py and tests/test_gpu_path_model.py.
 All CPU (`-m "not gpu"`); the GPU is bit-equal to the oracle by the parity tests, so what holds for the oracle holds for it.
 """
 import numpy as np

@@ -137,7 +137,7 @@ def test_depth3_path_tracer_vs_float64():
         cur = pos
         o2 = pos + sd_dir * 1e-5
         t2, tag2 = _hit_quads(o2, sd_dir, quads)
-        alive = alive & (tag2 >= 0)  # a miss ends the path (no env map)
+        alive = alive & (tag2 >= 0)  # a miss ends the path (no env map; tests/path_model.py has the miss branch with one)
         hp = o2 + sd_dir * t2[:, None]
         hl = alive & lightq[np.maximum(tag2, 0)]
         # emitter hit (:251-271): single-sided test on the INTERPOLATED normal (authored +y here): break if dot(norm, dir) < 0
