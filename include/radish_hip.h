@@ -128,6 +128,10 @@ typedef struct rdh_counters {
                                   the wavefront pipeline with material sort and three sub-frames for a big tree (>= 100 000 nodes) and a
                                   big share of the frame (>= 12 000 8x8 blocks: a 1080p frame, or half of one), else the persistent kernel
                                   (measured: DESIGN 5d, 8).  Same pixels either way; other structure bits are ignored with it */
+#define RDH_PT_WALK_ALL 131072u /* wavefront only: queue and walk every ray the path emits, in the reference's order of work.  By default a
+                                  frame skips the last bounce's extension rays that miss the box over the emissive triangles (scenes without
+                                  an environment map) and the shadow rays of light samples that contribute zero: same pixels, bit for bit.
+                                  RDH_PT_COUNT implies it, so the counters stay the reference's */
 #define RDH_PT_NO_SCHEDULE 32u /* persistent only: ignore the longest-paths-first block order of the previous launch   */
 #define RDH_PT_PROFILE 8u      /* bracket each launch of the traversal kernel (k_pt_persistent, k_wf_trace, or the megakernel)
                                   with hipEvents on the context's stream; read with rdh_profile_read.  With
@@ -587,6 +591,12 @@ int rdh_debug_persist_phases(rdh_ctx *ctx, uint64_t *out16);
  * capacity (in uint64_t) holds stages * waves * 3 of them, so a first call with capacity 0 sizes the second.  Blocking.
  * RDH_ERR_UNSUPPORTED otherwise. */
 int rdh_debug_wf_stamps(rdh_ctx *ctx, uint64_t *out, int64_t capacity, int32_t *stages, int32_t *waves);
+/* The rays the last wavefront pass of this context queued, summed over its pipelines: rays[k] = entries of trace(k)'s ray queue
+ * (k = 0: 64 per 8x8 block of the launch, off-frame pixels included), shadows[k] = shadow rays shade(k) queued for trace(k + 1),
+ * those on the first list included; k = 0 .. *stages - 1, *stages = maxDepth + 1 (0: no pass yet).  *stages is always set; the
+ * counts are written when capacity (entries of each array) holds them.  With RDH_PT_WALK_ALL or RDH_PT_COUNT that is every ray
+ * the reference traces; a default frame queues fewer (RDH_PT_WALK_ALL).  Blocking. */
+int rdh_debug_wf_counts(rdh_ctx *ctx, int32_t *rays, int32_t *shadows, int32_t capacity, int32_t *stages);
 
 /* Time of the most recent render call's kernels, measured with hipEvents on the context's stream (blocking);
  * the reference prints this figure from pathTrace (src/pathtrace.cu:364-374). */

@@ -43,6 +43,7 @@ RDH_PT_NO_PAIRS = 16384
 RDH_PT_NO_PACKETS = 8192
 RDH_PT_PAIRS = 32768
 RDH_PT_AUTO = 65536
+RDH_PT_WALK_ALL = 131072
 # BVH builders of rdh_build_bvh_device_ex / rdh_scene_update_geometry_ex (Context.build_bvh_device / update_geometry `builder`)
 RDH_BVH_SAH, RDH_BVH_LBVH = 0, 1
 BVH_BUILDERS = {"sah": RDH_BVH_SAH, "lbvh": RDH_BVH_LBVH}
@@ -62,6 +63,7 @@ EXPORTS = [
     "rdh_restir_read", "rdh_restir_read_scratch", "rdh_copy_image_to_pbo", "rdh_denoise_eaw", "rdh_denoise_svgf", "rdh_denoise_modulate",
     "rdh_denoise_add", "rdh_denoise_temporal_accumulate", "rdh_denoise_estimate_variance", "rdh_denoise_filter_variance", "rdh_restir_exchange_pack", "rdh_restir_exchange_unpack", "rdh_trace_closest", "rdh_trace_occluded", "rdh_counters_reset", "rdh_counters_read",
     "rdh_last_kernel_ms", "rdh_profile_reset", "rdh_profile_read", "rdh_debug_persist_stamps", "rdh_debug_persist_phases", "rdh_debug_wf_stamps",
+    "rdh_debug_wf_counts",
     "rdh_gbuffer_exchange_pack", "rdh_gbuffer_exchange_unpack", "rdh_comm_unique_id", "rdh_comm_init", "rdh_comm_destroy",
     "rdh_dump_rays", "rdh_set_occupancy_share", "rdh_allgather_tiles", "rdh_path_trace_gathered", "rdh_restir_exchange", "rdh_restir_direct_gathered", "rdh_gbuffer_exchange",
     "rdh_comm_init_all", "rdh_path_trace_gathered_all", "rdh_gbuffer_exchange_all", "rdh_restir_direct_gathered_all",
@@ -928,6 +930,19 @@ class Context:
         out = np.zeros((stages.value, waves.value, 6), dtype=np.uint64)
         self.check(fn(self.h, out.ctypes.data, out.size, C.byref(stages), C.byref(waves)))
         return out
+
+    def debug_wf_counts(self):
+        """(rays, shadows): int32 [maxDepth + 1] each, what the last wavefront pass queued per stage — rays[k] the entries of
+        trace(k)'s ray queue, shadows[k] the shadow rays shade(k) queued for trace(k + 1) (include/radish_hip.h).  (Bound here,
+        not in lib(): RADISH_HIP_LIB may name a build from before this entry.)"""
+        fn = lib().rdh_debug_wf_counts
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)], C.c_int32
+        stages = C.c_int32(0)
+        self.check(fn(self.h, None, None, 0, C.byref(stages)))
+        rays, shadows = np.zeros(stages.value, dtype=np.int32), np.zeros(stages.value, dtype=np.int32)
+        if stages.value:
+            self.check(fn(self.h, rays.ctypes.data, shadows.ctypes.data, stages.value, C.byref(stages)))
+        return rays, shadows
 
     def debug_persist_phases(self):
         out = np.zeros(16, dtype=np.uint64)

@@ -20,6 +20,7 @@
 #pragma once
 #include "kernels_pt.h"
 #include "wg_trace.h"
+#include "ray_cull.h"
 
 namespace rd {
 
@@ -42,6 +43,7 @@ struct WaveCounters {
     WaveCounter rayCount[kMaxWaveDepth + 2];     // rays of bounce k (written by raygen / shade(k-1))
     WaveCounter shadowCount[kMaxWaveDepth + 2];  // shadow rays emitted by shade(k)
     WaveCounter litCount[kMaxWaveDepth + 2];     // literal-class rays (both kinds) that shade(k-1) set aside for trace(k)
+    WaveCounter litShadowCount[kMaxWaveDepth + 2];  // shadow rays that shade(k) put on that list instead of shadowq (rdh_debug_wf_counts)
     WaveCounter traceHead[kMaxWaveDepth + 2];
     WaveCounter shadeHead[kMaxWaveDepth + 2][4];
     WaveCounter traceTicket[kMaxWaveDepth + 2][kTicketShards];  // workgroupTicket of trace(k) / shade(k)
@@ -116,6 +118,7 @@ struct WaveSlotPath {
     const int wr, q;   // write: set, slot
     int home;
     const bool delta;  // rd[rs][p].w, which the caller has loaded with the ray's direction
+    bool nullNee = false;  // setNee's sample adds nothing whatever its shadow ray finds: no kind, or a contribution of (+-0, +-0, +-0)
     RD_DEV v3 throughput() {
         const float4 t = w.thr[rs][p];
         home = __float_as_int(t.w);
@@ -127,7 +130,10 @@ struct WaveSlotPath {
     RD_DEV void setDirect(v3 v) { w.accD[home] = make_float4(v.x, v.y, v.z, 0.f); }
     RD_DEV void addIndirect(v3 v) { const float4 a = w.accI[home]; w.accI[home] = make_float4(a.x + v.x, a.y + v.y, a.z + v.z, 0.f); }
     RD_DEV Sampler rng(const DScene &s) const { const uint2 r = w.rng[rs][p]; return Sampler{s.sobol, r.x, (int)r.y}; }
-    RD_DEV void setNee(v3 c, float nw) { w.nee[wr][q] = make_float4(c.x, c.y, c.z, wfNeeTag(home, nw < 0.f ? kWfNeeNone : (nw == 0.f ? 0u : 1u))); }
+    RD_DEV void setNee(v3 c, float nw) {
+        w.nee[wr][q] = make_float4(c.x, c.y, c.z, wfNeeTag(home, nw < 0.f ? kWfNeeNone : (nw == 0.f ? 0u : 1u)));
+        nullNee = nw < 0.f || (c.x == 0.f && c.y == 0.f && c.z == 0.f);  // (float comparisons: either zero, never a NaN)
+    }
     RD_DEV void setPrevPos(v3 x) { w.prevPos[wr][q] = make_float4(x.x, x.y, x.z, 0.f); }
     RD_DEV void setRay(const Ray &ray, float pdf, bool deltaSample, v3 throughput, const Sampler &rng) {
         w.ro[wr][q] = make_float4(ray.o.x, ray.o.y, ray.o.z, pdf);
@@ -667,9 +673,35 @@ constexpr int kSortPacket = 64 * kSortChunks;    // records a wave bins at a tim
 #ifndef RD_WF_SHADE_WAVES
 #define RD_WF_SHADE_WAVES 1  // waves per SIMD k_wf_shade is held to (1: whatever its 147 VGPRs allow = 3)
 #endif
-__global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, WaveWorkspace w, int k, int maxDepth, int sorted) {
+// Rays that are not queued ("Rays whose outcome cannot reach the image"; walkAll != 0 — RDH_PT_WALK_ALL, and every
+// counting launch — queues them all, the reference's order of work):
+//   * RD_WF_CULL_LAST: the extension ray shade(maxDepth - 1) emits is walked by trace(maxDepth) only to learn whether it ends on an
+//     emitter — pathStep at k == maxDepth adds an emitter's radiance, or the environment's on a miss, and returns at the depth bound
+//     otherwise.  Without an environment map a ray that misses the padded box over the emissive triangles (emitBox, made by
+//     k_emitter_bounds earlier in this pass; ray_cull.h) adds nothing: it goes on neither rayq nor the first list, and shade(maxDepth)
+//     never sees its record.  The path's shadow ray of the same bounce is queued as ever.
+//   * RD_WF_SKIP_NULL_NEE: pathStep has a shadow ray traced for every NEE sample, also for one that can add nothing (no kind, or a
+//     contribution of zeros: the light below the horizon).  wfAddNee returns at once for the first, and adds zeros for the second
+//     to an accumulator that k_wf_raygen set to +0 and that only ever receives sums, so it is never -0 and a + (+-0) == a bit for
+//     bit.  Such a ray goes on neither shadowq nor the first list, and its target is not stored.
+#ifndef RD_WF_CULL_LAST
+#define RD_WF_CULL_LAST 1  // 0: queue every extension ray (measurements)
+#endif
+#ifndef RD_WF_SKIP_NULL_NEE
+#define RD_WF_SKIP_NULL_NEE 1  // 0: queue every shadow ray (measurements)
+#endif
+__global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, WaveWorkspace w, int k, int maxDepth, int sorted,
+                                                                     const float4 *__restrict__ emitBox, int walkAll) {
     __shared__ int sSorted[4][kSortPacket];  // per wave of the workgroup: the packet's path slots in class order
     WaveCounters *c = w.ctr;
+    // the last bounce's extension rays are tested against the emitter box (uniform loads, this stage only)
+    const bool cullLast = RD_WF_CULL_LAST && !walkAll && k + 1 == maxDepth && !hasEnvMap(s);
+    const bool skipNull = RD_WF_SKIP_NULL_NEE && !walkAll;
+    float4 boxLo = make_float4(0.f, 0.f, 0.f, 0.f), boxHi = boxLo;
+    if (cullLast) {
+        boxLo = emitBox[0];
+        boxHi = emitBox[1];
+    }
     const int wg = workgroupTicket(c->shadeTicket[k]);  // stands for blockIdx.x (see wavePull)
     const int lane = int(threadIdx.x & 63u);
     int *mySorted = sSorted[threadIdx.x >> 6];
@@ -752,14 +784,14 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
                 const PathStepResult r = pathStep(s, k, maxDepth, h.x, mk2(__int_as_float(h.y), __int_as_float(h.z)), mk3(rdw.x, rdw.y, rdw.z), st);
                 // the rays go to trace(k+1)'s queues below.  The two hints (trace classifies the ray it builds): some component of the
                 // direction below 1.1e-6 of its length
-                if (r.shadow) {
+                if (r.shadow && !(skipNull && st.nullNee)) {
                     w.sht[(k + 1) & 1][q] = make_float4(r.shadowTo.x, r.shadowTo.y, r.shadowTo.z, 0.f);
                     emitShadow = true;
                     const v3 dl = r.shadowTo - r.shadowFrom;
                     const float l2 = dot(dl, dl) * 1.21e-12f;
                     litShadow = dl.x * dl.x < l2 || dl.y * dl.y < l2 || dl.z * dl.z < l2;
                 }
-                if (r.extension) {
+                if (r.extension && !(cullLast && !mayReachEmitters(boxLo, boxHi, r.ray.o, r.ray.d))) {
                     emitRay = true;
                     litRay = fabs_(r.ray.d.x) < 1.1e-6f || fabs_(r.ray.d.y) < 1.1e-6f || fabs_(r.ray.d.z) < 1.1e-6f;
                 }
@@ -774,6 +806,10 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
                     int at = 0;
                     if (lane == 0) at = atomicAdd(lc, __popcll(m));
                     at = __shfl(at, 0, 64) + __popcll(m & laneMaskLt());
+                    if (kind == 0) {  // (rdh_debug_wf_counts: shadowCount does not hold the listed ones)
+                        const int listed = __popcll(__ballot(pred && at < w.litCap));
+                        if (lane == 0 && listed > 0) atomicAdd(&c->litShadowCount[k].v, listed);
+                    }
                     if (pred && at < w.litCap) {  // beyond the list's capacity the ray stays in its ordinary queue
                         lq[at] = kind == 0 ? (q | kWfLitShadow) : q;
                         if (kind == 0) emitShadow = false;  // nobody else reads the shadow queue

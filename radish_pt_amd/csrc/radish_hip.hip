@@ -121,6 +121,10 @@ struct SceneState {
     // rdh_scene_update_geometry
     int *dLightPrims = nullptr;      // the scene's current lightPrimIds (rdh_scene_set_materials rewrites it)
     int numLights = 0;
+    float4 *emitBox = nullptr;       // two float4: the padded box over the emissive triangles (k_emitter_bounds).  Made again, stream-
+                                     // ordered, by every wavefront pass that reads it, from the tris and dLightPrims of that moment: no
+                                     // edit entry has to remember it (made by the first such pass)
+    bool lightListPartial = false;   // the upload's light list was not "every Light triangle, ascending": no ray is tested against emitBox
     PairRec *updPairs = nullptr;     // pairs of an updated tree when the upload had none
     bool treePending = false;        // an update's header has not been folded into ds yet (settleTree)
 
@@ -242,6 +246,7 @@ struct rdh_ctx {
     long long wfCapacity = 0;   // path slots each workspace holds
     std::vector<void *> wfAllocs;
     hipEvent_t evWfFork = nullptr, evWfJoin = nullptr;
+    int wfLastStages = 0, wfLastParts = 0;  // of the last wavefront pass: maxDepth + 1, pipelines (rdh_debug_wf_counts)
 #ifdef RD_WF_STAMPS
     GrowBuf wfStamps{bufs};  // stamps (unsigned long long): k_wf_trace's, of the last wavefront pass (rdh_debug_wf_stamps)
     int wfStampStages = 0, wfStampWaves = 0;
@@ -817,6 +822,8 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
                        int maxDepth, uint32_t flags) {
     if (maxDepth > kMaxWaveDepth) return fail(c, RDH_ERR_ARGS, "maxDepth %d exceeds %d", maxDepth, kMaxWaveDepth);
     const bool count = (flags & RDH_PT_COUNT) != 0, sort = (flags & RDH_PT_SORT_MATERIAL) != 0;
+    // (the counters count the reference's order of work: every ray)
+    const bool walkAll = count || (flags & RDH_PT_WALK_ALL) != 0 || c->scene.lightListPartial;
     // Persistent kernels sized to what stays resident (k_wf_trace: 72 VGPRs, 7 waves per SIMD as 256-thread workgroups allow;
     // k_wf_shade 3 — tests/test_kernel_resources.py pins the budgets).  Their workgroups take their share of the work by ticket, in
     // the order they become resident (kernels_wave.h, wavePull), so a launch that is not alone on the chip loses nothing when
@@ -872,6 +879,19 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
         c->wfStampWaves = (int)(traceGrid * 4);
     }
 #endif
+    // The box over the emissive triangles that shade(maxDepth - 1) tests its extension rays against (kernels_wave.h,
+    // RD_WF_CULL_LAST): made here, on the context's stream before the fork, in every pass whose shade stage reads it, so it is the
+    // box of the triangles and the light list this pass renders whatever edit came before.  One workgroup over numLights
+    // triangles: 4-6 us per frame in the kernel trace of the teapots frame (profiles/ray_cull/trace_pr.txt).
+    if (!c->scene.emitBox)
+        if (int rc = sceneAlloc(c, &c->scene.emitBox, 2 * sizeof(float4))) return rc;
+    if (RD_WF_CULL_LAST && !walkAll && maxDepth >= 1 && c->scene.ds.envTex < 0) {
+        hipLaunchKernelGGL(k_emitter_bounds, dim3(1), dim3(256), 0, c->stream, c->scene.ds.tris, (const int *)c->scene.dLightPrims,
+                           c->scene.numLights, c->scene.ds.bvhSize > 0 ? c->scene.ds.nodes[0] : nullptr, c->scene.emitBox);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->wfLastStages = maxDepth + 1;
+    c->wfLastParts = parts;
     // RDH_PT_PROFILE with sub-frames: the pipelines' launches overlap by design, so what is timed is the FRAME — one event pair
     // from before the fork to after the join, on the context's stream (one pipeline: a pair around every k_wf_trace launch)
     const long pf = parts >= 2 ? profBegin(c, flags) : -1;
@@ -906,7 +926,8 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
                 hipLaunchKernelGGL((k_wf_trace<cnt.value, pr.value>), dim3(traceGrid), dim3(256), 0, st, c->scene.ds, w, k);
             }, count, tree);
             profEnd(c, pe);
-            hipLaunchKernelGGL(k_wf_shade, dim3(shadeGrid), dim3(256), 0, st, c->scene.ds, w, k, maxDepth, sort ? 1 : 0);
+            hipLaunchKernelGGL(k_wf_shade, dim3(shadeGrid), dim3(256), 0, st, c->scene.ds, w, k, maxDepth, sort ? 1 : 0,
+                               (const float4 *)c->scene.emitBox, walkAll ? 1 : 0);
         }
         keep(hipGetLastError(), "wavefront stage launch");
     }
@@ -1299,6 +1320,18 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
     c->scene.hostMats.assign(hm, hm + d->numMaterials);  // rdh_scene_set_materials edits these and counts emitters from them
     c->scene.matPrims.assign((size_t)d->numMaterials, 0);
     for (int p = 0; p < N; p++) c->scene.matPrims[(size_t)d->materialIds[p]]++;
+    {  // Is the caller's light list every triangle whose material is Light (what rdh_build_light_list makes)?  The upload is the
+       // one entry that takes a list from outside; only a complete one lets a frame skip rays that miss its box (emitBox).
+        long long emissive = 0;
+        for (int m = 0; m < d->numMaterials; m++)
+            if (hm[m].type == kMaterialLight) emissive += c->scene.matPrims[(size_t)m];
+        bool complete = emissive == d->numLights;
+        for (int i = 0; complete && i < d->numLights; i++) {
+            const int p = d->lightPrimIds[i];
+            complete = hm[d->materialIds[p]].type == kMaterialLight && (i == 0 || p > d->lightPrimIds[i - 1]);  // ascending: distinct
+        }
+        c->scene.lightListPartial = !complete;
+    }
     c->scene.edited.reset((size_t)d->numMaterials);
     c->scene.numTextures = d->numTextures;
     c->scene.texInfo.assign(texInfo.begin(), texInfo.begin() + d->numTextures);  // rdh_scene_set_texture checks sizes against these
@@ -2431,6 +2464,29 @@ int rdh_debug_wf_stamps(rdh_ctx *c, uint64_t *out, int64_t capacity, int32_t *st
 #else
     return fail(c, RDH_ERR_UNSUPPORTED, "library built without RD_WF_STAMPS");
 #endif
+}
+
+int rdh_debug_wf_counts(rdh_ctx *c, int32_t *rays, int32_t *shadows, int32_t capacity, int32_t *stages) {
+    if (!c || !stages || capacity < 0 || (capacity > 0 && (!rays || !shadows))) return RDH_ERR_ARGS;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the pass's pipelines have joined it
+    *stages = c->wfLastStages;
+    if (c->wfLastStages <= 0 || capacity < c->wfLastStages) return RDH_OK;
+    std::fill(rays, rays + c->wfLastStages, 0);
+    std::fill(shadows, shadows + c->wfLastStages, 0);
+    std::vector<WaveCounter> host(3 * (size_t)c->wfLastStages);
+    const size_t bytes = sizeof(WaveCounter) * (size_t)c->wfLastStages;
+    for (int h = 0; h < c->wfLastParts; h++) {
+        const WaveCounters *d = c->wf[h].ctr;
+        HIP_TRY(c, hipMemcpy(host.data(), d->rayCount, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(host.data() + c->wfLastStages, d->shadowCount, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(host.data() + 2 * c->wfLastStages, d->litShadowCount, bytes, hipMemcpyDeviceToHost));
+        for (int k = 0; k < c->wfLastStages; k++) {
+            rays[k] += host[k].v;
+            shadows[k] += host[c->wfLastStages + k].v + host[2 * c->wfLastStages + k].v;
+        }
+    }
+    return RDH_OK;
 }
 
 int rdh_copy_image_to_pbo(rdh_ctx *c, void *d_pbo, const void *d_image, int width, int height, int kind, int toneMapping,
