@@ -155,28 +155,21 @@ RD_DEV void waveAppend(bool pred, int item, int *queue, int *count) {
     if (pred) queue[base + __popcll(mask & laneMaskLt())] = item;
 }
 
-// The same for the 64-record chunks of one k_wf_shade packet at once: ONE returning atomic (they serialise chip-wide per
-// counter at ~12 ns; k_wf_shade's two appends per 64 records were most of its time).
-constexpr int kShadeChunks = 4;  // k_wf_shade: 64-record chunks per packet
+// k_wf_shade's appends.  Its packets are multiples of kShadePacket records; it appends what a wave has shaded to the two queues once
+// per RD_WF_APPEND_CHUNKS 64-record chunks and at the end of every packet, with ONE returning atomic per queue.  Until then a
+// record's entries wait as three bits in the wave's own sSorted row, in the place of the chunk it has just shaded (the slot is the
+// record's position, so it needs no storage), and nothing is carried beyond the packet: 16 = kSortChunks means once per packet.
+// Same-address returning atomics queue chip-wide per counter, and a wave cannot store its entries before it has the base: teapots
+// 1080p, 8 bounces, sorted, one pipeline, an append per 4 / 8 / 16 chunks: 6.81 / 6.70 / 6.70 ms a frame; stages 0-2 of this
+// kernel (packets of 512) 145 169 165 -> 127 148 141 us, the stages with packets of 256 unchanged (profiles/shade_appends/).
+// (Before that: an append per 64 records was most of the kernel's time.)
+constexpr int kShadeChunks = 4;  // k_wf_shade: 64-record chunks per smallest packet
 constexpr int kShadePacket = 64 * kShadeChunks;
-RD_DEV void waveAppendN(const bool (&pred)[kShadeChunks], const int (&item)[kShadeChunks], int *queue, int *count) {
-    unsigned long long m[kShadeChunks];
-    int total = 0;
-#pragma unroll
-    for (int j = 0; j < kShadeChunks; j++) {
-        m[j] = __ballot(pred[j]);
-        total += __popcll(m[j]);
-    }
-    if (total == 0) return;
-    int base = 0;
-    if ((threadIdx.x & 63u) == 0u) base = atomicAdd(count, total);
-    base = __shfl(base, 0, 64);
-#pragma unroll
-    for (int j = 0; j < kShadeChunks; j++) {
-        if (pred[j]) queue[base + __popcll(m[j] & laneMaskLt())] = item[j];
-        base += __popcll(m[j]);
-    }
-}
+#ifndef RD_WF_APPEND_CHUNKS
+#define RD_WF_APPEND_CHUNKS 16  // 4 / 8: measurements
+#endif
+static_assert(RD_WF_APPEND_CHUNKS == 4 || RD_WF_APPEND_CHUNKS == 8 || RD_WF_APPEND_CHUNKS == 16, "RD_WF_APPEND_CHUNKS: 4, 8 or 16");
+constexpr int kAppendSpan = 64 * RD_WF_APPEND_CHUNKS;  // records between two appends of a wave, at most
 
 // Work distribution for the persistent kernels.  Same-address returning atomics serialise chip-wide at ~12 ns each
 // (MI355X_MICROARCH.md "dequeue"/"fanin"), so (a) the FIRST share of the work is fixed by the logical index and costs no atomic,
@@ -671,7 +664,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PAIRS && !C
 constexpr int kSortChunks = 16;                  // chunks of 64 records per sorted packet
 constexpr int kSortPacket = 64 * kSortChunks;    // records a wave bins at a time
 #ifndef RD_WF_SHADE_WAVES
-#define RD_WF_SHADE_WAVES 1  // waves per SIMD k_wf_shade is held to (1: whatever its 147 VGPRs allow = 3)
+#define RD_WF_SHADE_WAVES 1  // waves per SIMD k_wf_shade is held to (1: whatever its 131 VGPRs allow = 3)
 #endif
 // Rays that are not queued ("Rays whose outcome cannot reach the image"; walkAll != 0 — RDH_PT_WALK_ALL, and every
 // counting launch — queues them all, the reference's order of work):
@@ -709,14 +702,7 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
         const int q = 0;
         const int n = c->rayCount[k].v;
         const int *hitq = w.rayq[k & 1];
-        // queue entries of the packet's chunks, held until its last chunk has been shaded, then appended together
-        int pendP[kShadeChunks], pendQ[kShadeChunks];  // the record's new slot; its ray-queue entry (-2 - slot: trace(k+1) has it on its first list)
-        bool pendShadow[kShadeChunks], pendRay[kShadeChunks];
-#pragma unroll
-        for (int j = 0; j < kShadeChunks; j++) {
-            pendP[j] = pendQ[j] = -1;
-            pendShadow[j] = pendRay[j] = false;
-        }
+        int pendShadows = 0, pendRays = 0;  // entries waiting in the wave's sSorted row for the next append (wave-uniform)
         // unsorted: packets of kShadePacket = 256 records.  sorted: 256 .. kSortPacket = 1 024 records (multiples of 256), as large
         // as still leaves every wave about two packets — with one big packet per wave there is no dynamic balancing left and a
         // short queue (the Cornell frame after bounce 1) would keep nine waves in ten idle while the others shade 16 chunks each
@@ -817,23 +803,28 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
                     }
                 }
             }
-            {
-                const int j = ((sub >> 6) - 1) & (kShadeChunks - 1);  // chunk just shaded, within its group of four (wave-uniform)
-#pragma unroll
-                for (int jj = 0; jj < kShadeChunks; jj++)
-                    if (jj == j) {
-                        pendP[jj] = q;
-                        pendQ[jj] = rayFirst ? -2 - q : q;
-                        pendShadow[jj] = emitShadow;
-                        pendRay[jj] = emitRay;
-                    }
-            }
-            // every fourth chunk, and at the last chunk of the queue (the loop then leaves or pulls the next packet): append
-            if ((sub & (kShadePacket - 1)) == 0 || base + sub >= n) {
-                waveAppendN(pendShadow, pendP, w.shadowq, &c->shadowCount[k].v);
-                waveAppendN(pendRay, pendQ, w.rayq[(k + 1) & 1], &c->rayCount[k + 1].v);
-#pragma unroll
-                for (int jj = 0; jj < kShadeChunks; jj++) pendShadow[jj] = pendRay[jj] = false;
+            // (the lane has read its entry of this chunk from the row above: the place is free until the next packet is binned)
+            mySorted[subNow + lane] = (emitShadow ? 1 : 0) | (emitRay ? 2 : 0) | (rayFirst ? 4 : 0);
+            pendShadows += __popcll(__ballot(emitShadow));
+            pendRays += __popcll(__ballot(emitRay));
+            if ((sub & (kAppendSpan - 1)) == 0 || sub == packet || base + sub >= n) {
+                int atS = 0, atR = 0;  // both atomics are in flight together
+                if (lane == 0) {
+                    if (pendShadows > 0) atS = atomicAdd(&c->shadowCount[k].v, pendShadows);
+                    if (pendRays > 0) atR = atomicAdd(&c->rayCount[k + 1].v, pendRays);
+                }
+                atS = __builtin_amdgcn_readfirstlane(atS);
+                atR = __builtin_amdgcn_readfirstlane(atR);
+                int *nextq = w.rayq[(k + 1) & 1];
+                for (int o = subNow & ~(kAppendSpan - 1); o < sub; o += 64) {  // the chunks shaded since the last append
+                    const int f = mySorted[o + lane], qq = base + o + lane;
+                    const unsigned long long mS = __ballot((f & 1) != 0), mR = __ballot((f & 2) != 0);
+                    if (f & 1) w.shadowq[atS + __popcll(mS & laneMaskLt())] = qq;
+                    if (f & 2) nextq[atR + __popcll(mR & laneMaskLt())] = (f & 4) ? -2 - qq : qq;
+                    atS += __popcll(mS);
+                    atR += __popcll(mR);
+                }
+                pendShadows = pendRays = 0;
             }
         }
     }
