@@ -428,6 +428,44 @@ int rdh_path_trace(rdh_ctx *ctx, float *d_directIllum, float *d_indirectIllum, i
  * honoured as in rdh_path_trace (packed tiles).  The last-kernel time covers all passes (wavefront) or the last launch (others). */
 int rdh_path_trace_samples(rdh_ctx *ctx, float *d_directIllum, float *d_indirectIllum, int iter, int looper, int numSamples,
                            int samplesPerPass, int maxDepth, uint32_t flags);
+/* ---- adaptive sampling: per-pixel sample counts in one wavefront pass ---- */
+#define RDH_ADAPTIVE_MAX_REQUEST 16 /* samples of one pixel in one pass: the most DESIGN 5f measured in one pass */
+/* Trace a request plane.  All planes are in frame layout (y*W+x): d_sampleCount[p] is how many samples pixel p's running means hold
+ * (it plays `iter`, per pixel), d_request[p] how many more to take now, 0..RDH_ADAPTIVE_MAX_REQUEST.  d_moments may be null; else it
+ * is float[H*W][2], the running means of L and L*L, L = luminance(finishSample(direct) + finishSample(indirect)) of each sample,
+ * folded with the running mean's expression (m * float(n) + x) / float(n + 1).
+ * Contract.  After the call, for every pixel with r = request[p] > 0 and c = count[p]: the two images at p are bit for bit those of
+ *     for j in 0..r-1: rdh_path_trace(ctx, d, i, iter = c + j, looper = (looper + c + j) % 10000, maxDepth, flags)
+ * count[p] = c + r, and the moments are folded alike: every pixel walks its own Sobol rows however unevenly the frame is sampled.
+ * A pixel with request[p] == 0 is not read beyond its request and not written in any plane.  With every request r and every count
+ * c the call is rdh_path_trace_samples(.., iter = c, (looper + c) % 10000, numSamples = r, ..), work counters included; with
+ * RDH_PT_COUNT the counters are those of the requested (pixel, sample) pairs and nothing else.  *samplesTraced (may be null)
+ * receives the plane's sum T.
+ * The requested pairs become a dense slot list (pixel-major inside 8x8-block order), made by an ordered count / scan / scatter on
+ * the device, and the wavefront stages run over it: the cost of a call follows T, not the frame.  T is known only after the scan:
+ * the entry reads it, together with the device's error flag, in one blocking copy — ONE host synchronisation per call — and sizes
+ * the workspace and the grids by it.  T == 0: nothing more is launched, nothing written, RDH_OK.  A request outside
+ * 0..RDH_ADAPTIVE_MAX_REQUEST, or a requested pixel's count negative or overflowing int32 with its request: RDH_ERR_ARGS, nothing
+ * traced, no plane written.  T beyond what one pass holds (fewer than 2^30 slots, 4 GiB of them: rdh_path_trace_samples):
+ * RDH_ERR_ARGS with T and the limit in rdh_last_error, nothing allocated; the caller lowers its step.
+ * Always one pipeline: RDH_PT_WF_SUBFRAMES is accepted and ignored, because the slot list is dense already.  RDH_PT_SORT_MATERIAL,
+ * RDH_PT_COUNT, RDH_PT_PAIRS / RDH_PT_NO_PAIRS, RDH_PT_WALK_ALL, RDH_PT_WF_SMALL_LISTS and RDH_PT_PROFILE mean what they mean in
+ * rdh_path_trace.  Refused before anything is enqueued: without RDH_PT_WAVEFRONT, or with RDH_PT_PERSISTENT or RDH_PT_AUTO,
+ * RDH_ERR_UNSUPPORTED; a tile partition with world > 1 RDH_ERR_UNSUPPORTED; null images, counts or requests, a maxDepth or looper
+ * rdh_path_trace refuses: RDH_ERR_ARGS; RDH_ERR_NO_SCENE as there. */
+int rdh_path_trace_adaptive(rdh_ctx *ctx, float *d_directIllum, float *d_indirectIllum, int32_t *d_sampleCount,
+                            const int32_t *d_request, float *d_moments, int looper, int maxDepth, uint32_t flags,
+                            int64_t *samplesTraced);
+/* Decide the requests on the device from the counts and moments above.  All float32, in this order: with n = count[p], m1 and m2
+ * the pixel's moments, a pixel WANTS samples if n < minSamples, or if err2 > tol * tol with var = m2 - m1 * m1,
+ * err2 = var / float(n), tol = threshold * (m1 + 0.01f) (false for NaN).  An 8x8 block (the renderer's own blocks) is ACTIVE if any
+ * of its pixels wants; every pixel of an active block with n < maxSamples gets request = min(step, maxSamples - n), every other
+ * pixel 0.  `out` (may be null) receives the sums over the frame through one blocking read; with null the call is asynchronous.
+ * step outside 1..RDH_ADAPTIVE_MAX_REQUEST, minSamples < 0, maxSamples < minSamples, a threshold that is negative or not finite,
+ * null planes: RDH_ERR_ARGS.  Needs the camera (its resolution) and no scene; a tile partition with world > 1: RDH_ERR_UNSUPPORTED. */
+typedef struct rdh_adaptive_stats { int64_t samplesRequested; int32_t activeBlocks; int32_t wantingPixels; } rdh_adaptive_stats;
+int rdh_adaptive_plan(rdh_ctx *ctx, const int32_t *d_sampleCount, const float *d_moments, int32_t *d_request,
+                      int minSamples, int maxSamples, int step, float threshold, rdh_adaptive_stats *out);
 /* Replaces pathTraceDirect(glm::vec3*, int) (src/pathtrace.cu:387-407). */
 int rdh_path_trace_direct(rdh_ctx *ctx, float *d_directIllum, int iter, int looper, uint32_t flags);
 /* Replaces GBuffer::render(DevScene*, const Camera&) (src/gBuffer.cu:83-103). */

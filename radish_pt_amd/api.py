@@ -77,6 +77,7 @@ EXPORTS = [
     "rdh_scene_set_materials", "rdh_build_light_list_device",
     "rdh_scene_set_texture", "rdh_scene_env_power", "rdh_debug_read_textures",
     "rdh_scene_set_geometry", "rdh_debug_read_geometry",
+    "rdh_path_trace_adaptive", "rdh_adaptive_plan",
 ]
 
 
@@ -117,6 +118,13 @@ class CountersC(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class AdaptiveStatsC(C.Structure):  # rdh_adaptive_stats
+    _fields_ = [("samplesRequested", C.c_int64), ("activeBlocks", C.c_int32), ("wantingPixels", C.c_int32)]
+
+
+RDH_ADAPTIVE_MAX_REQUEST = 16
 
 
 class RestirParamsC(C.Structure):
@@ -222,6 +230,16 @@ def lib():
             fn.argtypes, fn.restype = args, res
         _lib = l
     return _lib
+
+
+def adaptive_entries():
+    """(rdh_path_trace_adaptive, rdh_adaptive_plan) with their signatures.  Bound here, at first use, not in lib(): RADISH_HIP_LIB
+    may name a build from before these entries (the parent's library of an A/B run), which everything else must still load."""
+    vp, i32 = C.c_void_p, C.c_int32
+    trace, plan = lib().rdh_path_trace_adaptive, lib().rdh_adaptive_plan
+    trace.argtypes, trace.restype = [vp, vp, vp, vp, vp, vp, i32, i32, C.c_uint32, C.POINTER(C.c_int64)], i32
+    plan.argtypes, plan.restype = [vp, vp, vp, vp, i32, i32, i32, C.c_float, C.POINTER(AdaptiveStatsC)], i32
+    return trace, plan
 
 
 class RadishError(RuntimeError):
@@ -666,6 +684,47 @@ class Context:
         self.check(lib().rdh_path_trace_samples(self.h, self._ptr(direct, n, "pathTraceSamples: directIllum"),
                                                 self._ptr(indirect, n, "pathTraceSamples: indirectIllum"), iter, looper, samples,
                                                 samples_per_pass, max_depth, flags))
+
+    # ---- adaptive sampling (rdh_path_trace_adaptive, rdh_adaptive_plan): planes in frame layout ----
+    def path_trace_adaptive(self, direct, indirect, counts, requests, looper, max_depth, flags, moments=None):
+        """requests[p] more samples of every pixel p (0..16) in one wavefront pass: pixel p's images afterwards are those of path_trace
+        at iter counts[p] + j, looper (looper + counts[p] + j) % 10000, j = 0..requests[p]-1; counts[p] grows by requests[p] and the
+        moments (float32 [H*W, 2], running means of the samples' luminance and its square; may be None) are folded alike.  Pixels
+        without a request are not written.  Returns the samples traced (the plane's sum).  One host synchronisation."""
+        torch = _torch()
+        px = self.width * self.height
+        traced = C.c_int64(0)
+        self.check(adaptive_entries()[0](
+            self.h, self._ptr(direct, 3 * px, "pathTraceAdaptive: directIllum"), self._ptr(indirect, 3 * px, "pathTraceAdaptive: indirectIllum"),
+            self._ptr(counts, px, "pathTraceAdaptive: counts", torch.int32), self._ptr(requests, px, "pathTraceAdaptive: requests", torch.int32),
+            None if moments is None else self._ptr(moments, 2 * px, "pathTraceAdaptive: moments"), looper, max_depth, flags,
+            C.byref(traced)))
+        return int(traced.value)
+
+    def adaptive_plan(self, counts, moments, requests, min_samples, max_samples, step, threshold):
+        """Fill requests (int32 [H*W]) from counts and moments (rdh_adaptive_plan): every pixel of an 8x8 block in which some pixel
+        has fewer than min_samples samples, or a relative standard error of its mean luminance above threshold, gets
+        min(step, max_samples - count), every other pixel 0.  Returns {"samplesRequested", "activeBlocks", "wantingPixels"}."""
+        torch = _torch()
+        px = self.width * self.height
+        st = AdaptiveStatsC()
+        self.check(adaptive_entries()[1](
+            self.h, self._ptr(counts, px, "adaptivePlan: counts", torch.int32), self._ptr(moments, 2 * px, "adaptivePlan: moments"),
+            self._ptr(requests, px, "adaptivePlan: requests", torch.int32), min_samples, max_samples, step, threshold, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+    def converge(self, direct, indirect, counts, moments, looper, max_depth, flags, min_samples, max_samples, step, threshold, max_passes):
+        """Plan and trace in turn, at most max_passes times, until the plan asks for nothing.  Returns the plans' statistics, one dict
+        per plan made (the last one has samplesRequested == 0 when the frame has converged within max_passes)."""
+        torch = _torch()
+        requests = torch.zeros(self.width * self.height, dtype=torch.int32, device=counts.device)
+        passes = []
+        for _ in range(max_passes):
+            passes.append(self.adaptive_plan(counts, moments, requests, min_samples, max_samples, step, threshold))
+            if passes[-1]["samplesRequested"] == 0:
+                break
+            self.path_trace_adaptive(direct, indirect, counts, requests, looper, max_depth, flags, moments=moments)
+        return passes
 
     def path_trace_direct(self, direct, iter, looper, flags=0):
         n = self._image_elems() if self.width else 0

@@ -15,6 +15,9 @@
 // the CPU oracle by bits (tests/test_gpu_shim_runs.py).  What does not: real glm and the real reference headers, and more
 // than one GPU.  (The Python mirror radish_pt_amd/api.py is the host side the other GPU tests and bench.py exercise.)
 //
+// Adaptive sampling (rdh_path_trace_adaptive, rdh_adaptive_plan) has no counterpart here: the reference samples every
+// pixel alike and has no signature to keep.
+//
 // Macros:  RADISH_SHIM_NO_REFERENCE_HEADERS  the including file has already declared glm / Camera / GBuffer / Scene /
 //                                            Settings / State (skip the reference's #includes)
 //          RADISH_SHIM_HELPERS_ONLY          only namespace radish_shim (no free functions)
