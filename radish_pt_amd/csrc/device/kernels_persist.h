@@ -23,7 +23,6 @@
 // 84 B per lane, so the traversal loop runs on the walker's registers alone.
 #pragma once
 #include "kernels_pt.h"
-#include "wg_trace.h"
 
 namespace rd {
 
@@ -41,9 +40,6 @@ namespace rd {
 // in the drain measured 1 % faster on the Cornell frame, 4 / 8 64ths 3 % / 1.5 % slower; with RD_SHADE_MIN = 32 the two coincide.
 #ifndef RD_SHADE_MIN_DRAIN
 #define RD_SHADE_MIN_DRAIN 32
-#endif
-#ifndef RD_PIX_REFILL_MIN
-#define RD_PIX_REFILL_MIN 16
 #endif
 
 constexpr int kDeferCap = 256;  // rays k_gbuffer_literal takes: one per workgroup, one round
@@ -596,331 +592,6 @@ __global__ __launch_bounds__(64, PAIRS && !COUNT ? RD_PERSIST_PAIR_WAVES : RD_PE
     }
 #endif
     if (COUNT) flushCounters(s.counters, nClosest, nAny, nHits, ws);
-}
-
-// ---- renderGBuffer as a persistent launch (gBuffer.cu:3-76) -------------------------------------------------------------
-// k_gbuffer (kernels_pt.h) binds a pixel to a lane for the whole launch, so every wave waits for the longest of its 64
-// primary rays (measured on the teapots scene: 2.97 ms for 2.07 M rays, a quarter of k_pt_persistent's rate).  Here lanes
-// are refilled: a lane whose ray has ended writes its G-buffer record (batched: once 16 lanes wait) and takes the next
-// pixel.  Same centre ray, same walk, same record per pixel as k_gbuffer.
-// One pixel's G-buffer record (gBuffer.cu:28-67), from the primary ray's closest hit.
-RD_DEV void gbufStore(const DScene &s, const DCamera &cam, const DCamera &lastCam, const GBufPtrs &gb, int idx, const RaySlab &rs,
-                      int hitPrim, v2 hitBary) {
-    if (hitPrim != -1) {
-        Surface isec;
-        fetchSurface(s, hitPrim, hitBary, isec);
-        // first, while prim and bary are live anyway: kept to the end they cost k_gbuffer_packet its seventh wave (75 VGPRs for 72)
-        gb.motion[idx] = gbufMotionIndex(cam, lastCam, gb, isec, hitBary);
-        int matId = isec.matId;
-        if (loadMaterial(s.mats, isec.matId).type == Light) matId = -2;  // NullPrimitive - 1 (gBuffer.cu:33-37)
-        Material material = texturedMaterial(s, isec);                  // :44 (may perturb isec.norm)
-        store3(gb.albedo, idx, material.baseColor);
-        store3(gb.normal, idx, isec.norm);
-        gb.primId[idx] = matId;
-        gb.depth[idx] = length(rs.o - isec.pos);
-    } else {
-        store3(gb.albedo, idx, hasEnvMap(s) ? envLookup(s, rs.d) : mk3(0.f));  // :61-66
-        store3(gb.normal, idx, mk3(0.f));
-        gb.primId[idx] = -1;
-        gb.depth[idx] = 1.f;
-        gb.motion[idx] = 0;
-    }
-}
-
-// The un-jittered centre ray of pixel (x, y) (gBuffer.cu:11-26).
-RD_DEV Ray gbufPrimaryRay(const DCamera &cam, int x, int y) {
-    float aspect = float(cam.resx) / float(cam.resy);
-    v2 pixelsize = {1.f / float(cam.resx), 1.f / float(cam.resy)};
-    v2 scr = mk2(float(x), float(y)) * pixelsize;
-    v2 ruv = scr + pixelsize * mk2(0.5f, 0.5f);
-    ruv = {1.f - ruv.x * 2.f, 1.f - ruv.y * 2.f};
-    v3 pLens = mk3(0.f);
-    v2 f = (ruv * mk2(aspect, 1.f)) * cam.tanFovY;
-    v3 pFocus = mk3(f.x, f.y, 1.f) * cam.focalDist;
-    v3 dir = pFocus - pLens;
-    Ray ray;
-    ray.o = cam.position + cam.right * pLens.x + cam.up * pLens.y;
-    ray.d = normalize(mul(m3{cam.right, cam.up, cam.view}, dir));
-    return ray;
-}
-
-#ifndef RD_GB_FINISH_MIN
-#define RD_GB_FINISH_MIN 16
-#endif
-// PAIRS: the primary rays walk the sibling pairs (traverse.h, pairStep).  Coherent rays gain nothing from it while the threaded arrays
-// sit in the caches (teapots, 201 k nodes: 0.78 ms either way) — the host picks it for trees whose six threaded arrays outgrow the
-// Infinity Cache (radish_hip.hip, rdh_gbuffer_render).
-template <bool COUNT, bool DEFER, bool PAIRS = false>
-__global__ __launch_bounds__(64, PAIRS && !COUNT ? 4 : 1) void k_gbuffer_persistent(DScene s, DCamera cam, DCamera lastCam, PixelMap pm, GBufPtrs gb,
-                                                           PersistCounters *pc, int2 *__restrict__ pairOvf = nullptr, int pairOvfDepth = 0) {
-    __shared__ int2 sStack[PAIRS ? kPairLds * 64 : 1];  // PAIRS: the lanes' stacks (traverse.h, pairPush)
-    int2 *const ovf = PAIRS ? pairOvf + (size_t)blockIdx.x * (size_t)pairOvfDepth * 64 : nullptr;
-    const int lane = int(threadIdx.x) & 63;
-    const int end = s.bvhSize;
-    const int numBlocks = pm.numBlocks;
-    const int paddedBlocks = int((((unsigned)(numBlocks + 3) / 4u + 7u) / 8u) * 8u * 4u);
-    WalkStats ws{0, 0};
-    unsigned nClosest = 0, nHits = 0;
-    int curBlock = int(blockIdx.x);
-    int slotNext = 0;
-    const int gridWavesN = int(gridDim.x);
-    bool exhausted = curBlock >= paddedBlocks;
-
-    constexpr int G_IDLE = 0, G_TRACE = 1, G_DONE = 2;
-    int state = G_IDLE;
-    int pixIdx = 0;
-    RaySlab rs;
-    rs.o = rs.d = rs.inv = mk3(0.f);
-    rs.cls = 0;
-    const NodeRec *nodes = s.nodes[0];
-    int node = end, pending = -1;  // PAIRS: `node` is the pair to enter next (pairStep's `cur`)
-    int ord = 0;
-    PairStack stack{0, 0};
-    float tmax = 0.f;
-    int hitPrim = -1;
-    v2 hitBary = mk2(0.f, 0.f);
-    const bool deferAll = DEFER && pc->deferCount <= kDeferCap;  // written by k_gbuffer_find_literal, earlier in the stream
-    auto walkOver = [&]() { return PAIRS ? (node == kPairNone && stack.sp == 0) : (node == end); };
-
-    for (;;) {
-        // ---------------- new pixels for idle lanes ----------------
-        const unsigned long long idleM = __ballot(state == G_IDLE);
-        const int nIdle = __popcll(idleM);
-        if (!exhausted && nIdle >= RD_PIX_REFILL_MIN) {
-            const int myRank = __popcll(idleM & laneMaskLt());
-            int taken = 0;
-            while (taken < nIdle && !exhausted) {
-                if (slotNext == 64) {
-                    int b = 0;
-                    if (lane == 0) b = atomicAdd(&pc->blockHead, 1);
-                    curBlock = __shfl(b, 0, 64) + gridWavesN;
-                    slotNext = 0;
-                    if (curBlock >= paddedBlocks) {
-                        exhausted = true;
-                        break;
-                    }
-                }
-                const int avail = 64 - slotNext;
-                const int give = (nIdle - taken) < avail ? (nIdle - taken) : avail;
-                if (state == G_IDLE && myRank >= taken && myRank < taken + give) {
-                    unsigned wgLogical;
-                    const bool ok = xcdSwizzle((unsigned)curBlock >> 2, (unsigned)(numBlocks + 3) >> 2, wgLogical);
-                    const unsigned blk = ok ? wgLogical * 4u + ((unsigned)curBlock & 3u) : 0xffffffffu / 64u;
-                    Pix px = mapPixel(pm, blk, (unsigned)(slotNext + (myRank - taken)));
-                    if (px.valid && ok) {
-                        pixIdx = px.index;
-                        Ray ray = gbufPrimaryRay(cam, px.x, px.y);
-                        rs = makeRaySlab(ray);
-                        nodes = s.nodes[getMTBVHId(-ray.d)];
-                        node = 0;
-                        pending = -1;
-                        hitPrim = -1;
-                        tmax = 3.402823466e+38f;
-                        if (DEFER && raySetAside(rs.cls) && end != 0 && deferAll) {
-                            // a literal-class ray: k_gbuffer_literal has it (found by k_gbuffer_find_literal)
-                        } else {
-                            nClosest++;
-                            state = G_TRACE;
-                            if (PAIRS) {
-                                ord = getMTBVHId(-ray.d);
-                                stack = PairStack{0, 0};
-                                if (rs.cls == 0 || end == 0) pairStart<COUNT>(s, rs, tmax, node, pending, ws);  // the root's box
-                                else node = kPairFresh;  // a literal-class ray: traced whole below
-                            }
-                        }
-                    }
-                }
-                slotNext += give;
-                taken += give;
-            }
-        }
-        if (__ballot(state != G_IDLE) == 0ull) {
-            if (exhausted) break;
-            continue;
-        }
-        // ---------------- literal-class rays: traced whole by the whole wave ----------------
-        {
-            unsigned long long lit = __ballot(PAIRS ? (state == G_TRACE && node == kPairFresh)
-                                                    : (state == G_TRACE && rs.cls != 0 && node == 0 && pending < 0 && end != 0));
-            while (lit) {
-                const int L = __ffsll((long long)lit) - 1;
-                lit &= lit - 1ull;
-                CoopTrace ct = coopTraceWhole<false>(s, readlanePtr(nodes, L), readlaneRay(rs, L), readlaneF(tmax, L));
-                if (lane == L) {
-                    hitPrim = ct.hitPrim;
-                    hitBary = ct.bary;
-                    tmax = ct.tmax;
-                    node = PAIRS ? kPairNone : end;
-                    if (COUNT) {
-                        ws.nodes += ct.nodes;
-                        ws.tris += ct.tris;
-                    }
-                }
-            }
-        }
-        // ---------------- box steps ----------------
-        if (PAIRS) {
-            bool busy = state == G_TRACE && pending < 0 && !walkOver();
-            const int nStart = __popcll(__ballot(busy));
-            if (nStart > 0) {
-                const int minWalk = (nStart * (RD_LEAF_DEN - RD_LEAF_NUM) + RD_LEAF_DEN - 1) / RD_LEAF_DEN;
-                do {
-                    pairPopOne<COUNT>(sStack, lane, ovf, tmax, busy, node, stack, pending, ws);
-                    if (busy && node >= 0) {
-                        pairStep<COUNT>(s.pairs, sStack, lane, ovf, rs, tmax, ord, node, stack, pending, ws);
-                        busy = pending < 0 && (node >= 0 || stack.sp > 0);
-                    }
-                } while (__popcll(__ballot(busy)) >= (minWalk > 1 ? minWalk : 1));
-            }
-        } else {
-            bool walking = state == G_TRACE && pending < 0 && node != end;
-            const int nStart = __popcll(__ballot(walking));
-            if (nStart == 1) {
-                const int L = __ffsll((long long)__ballot(walking)) - 1;
-                CoopResult cr = coopWalk(readlanePtr(nodes, L), readlaneI(node, L), end, readlaneRay(rs, L), readlaneF(tmax, L),
-                                         RD_COOP_WINDOWS);
-                if (lane == L) {
-                    node = cr.node;
-                    pending = cr.pending;
-                    if (COUNT) ws.nodes += cr.visited;
-                }
-            } else if (nStart > 0) {
-                const int minWalk = (nStart * (RD_LEAF_DEN - RD_LEAF_NUM) + RD_LEAF_DEN - 1) / RD_LEAF_DEN;
-                do {
-                    if (walking) {
-                        float4 lo = nodes[node].lo_prim;
-                        float4 hi = nodes[node].hi_next;
-                        float boundDist;
-                        if (COUNT) ws.nodes++;
-                        bool boundHit = aabbFast(lo, hi, rs, boundDist);
-                        if (boundHit && boundDist < tmax) {
-                            pending = __float_as_int(lo.w);
-                            node++;
-                        } else {
-                            node = __float_as_int(hi.w);
-                        }
-                        walking = pending < 0 && node != end;
-                    }
-                } while (__popcll(__ballot(walking)) >= (minWalk > 1 ? minWalk : 1));
-            }
-        }
-        // ---------------- leaf tests ----------------
-        if (state == G_TRACE && pending >= 0) {
-            TriVerts tv = loadTri(s.tris, pending);
-            float dist;
-            v2 bary;
-            if (COUNT) ws.tris++;
-            bool hit = intersectTriangle(rs, tv.a, tv.b, tv.c, bary, dist);
-            if (hit && dist < tmax) {
-                hitPrim = pending;
-                tmax = dist;
-                hitBary = bary;
-            }
-            pending = -1;
-        }
-        if (state == G_TRACE && pending < 0 && walkOver()) state = G_DONE;
-        // ---------------- write the records of finished pixels ----------------
-        {
-            const unsigned long long doneM = __ballot(state == G_DONE);
-            const int nBusy = __popcll(__ballot(state != G_IDLE));
-            if (doneM != 0ull && __popcll(doneM) * 64 >= nBusy * RD_GB_FINISH_MIN) {
-                if (state == G_DONE) {
-                    if (hitPrim != -1) nHits++;
-                    gbufStore(s, cam, lastCam, gb, pixIdx, rs, hitPrim, hitBary);
-                    state = G_IDLE;
-                }
-            }
-        }
-    }
-    if (COUNT) flushCounters(s.counters, nClosest, 0u, nHits, ws);
-}
-
-// ---- renderGBuffer with the primary rays of an 8x8 block walked as a PACKET (traverse.h, packetWalk) ---------------------------------
-// Centre rays of neighbouring pixels make nearly the same walk (teapots camera: 89 visits per ray, 107 different nodes per block), so
-// a wave takes one block, walks the union once with one uniform node load per visit, and writes its 64 records.  No lane refill,
-// no persistent grid: a wave's work is one short walk.  Same centre ray, same visits, same record per pixel as k_gbuffer.
-template <bool COUNT, bool DEFER>
-__global__ __launch_bounds__(256) void k_gbuffer_packet(DScene s, DCamera cam, DCamera lastCam, PixelMap pm, GBufPtrs gb, const PersistCounters *pc,
-                                                        int budget) {
-    const int lane = int(threadIdx.x) & 63;
-    const unsigned blk = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (blk >= (unsigned)pm.numBlocks) return;
-    const int end = s.bvhSize;
-    const Pix px = mapPixel(pm, blk, (unsigned)lane);
-    WalkStats ws{0, 0};
-    unsigned nClosest = 0, nHits = 0;
-    const bool deferAll = DEFER && pc->deferCount <= kDeferCap;  // written by k_gbuffer_find_literal, earlier in the stream
-    Ray ray{mk3(0.f), mk3(0.f, 0.f, 1.f)};
-    if (px.valid) ray = gbufPrimaryRay(cam, px.x, px.y);
-    const RaySlab rs = makeRaySlab(ray);
-    const int ord = getMTBVHId(-ray.d);
-    float tmax = 3.402823466e+38f;
-    int hitPrim = -1;
-    v2 hitBary = mk2(0.f, 0.f);
-    const bool traced = px.valid && !(DEFER && raySetAside(rs.cls) && end != 0 && deferAll);  // else: k_gbuffer_literal has this pixel
-    if (traced) nClosest++;
-    unsigned long long lit = __ballot(traced && rs.cls != 0 && end != 0);
-    while (lit) {  // literal-class rays kept here: traced whole by the wave, one after the other
-        const int L = __ffsll((long long)lit) - 1;
-        lit &= lit - 1ull;
-        const NodeRec *nodes = s.nodes[0] + (size_t)readlaneI(ord, L) * (size_t)(end + 1);
-        CoopTrace ct = coopTraceWhole<false>(s, nodes, readlaneRay(rs, L), readlaneF(tmax, L));
-        if (lane == L) {
-            hitPrim = ct.hitPrim;
-            hitBary = ct.bary;
-            tmax = ct.tmax;
-            if (COUNT) {
-                ws.nodes += ct.nodes;
-                ws.tris += ct.tris;
-            }
-        }
-    }
-    packetWalkAll<COUNT>(s, traced && rs.cls == 0 && end != 0, ord, rs, tmax, hitPrim, hitBary, ws, budget);
-    if (traced) {
-        if (hitPrim != -1) nHits++;
-        gbufStore(s, cam, lastCam, gb, px.index, rs, hitPrim, hitBary);
-    }
-    if (COUNT) flushCounters(s.counters, nClosest, 0u, nHits, ws);
-}
-
-// Literal-class primary rays are traced apart, each by a whole 1 024-thread workgroup (wg_trace.h), in a launch that runs
-// BESIDE k_gbuffer_persistent on a second stream: traced in place by one wave, one such ray takes 1.2 ms on the teapots scene,
-// twice the rest of the pass.  The ray's class depends on the camera and the pixel only, so a first tiny kernel lists them;
-// when there are more than kDeferCap (an axis-aligned camera makes a whole pixel row such rays) none is set aside — many
-// one-wave traces in parallel are the better use of the chip then.
-__global__ __launch_bounds__(256) void k_gbuffer_find_literal(DScene s, DCamera cam, PixelMap pm, PersistCounters *pc) {
-    const int idx = int(blockIdx.x * blockDim.x + threadIdx.x);
-    if (idx >= cam.resx * cam.resy || s.bvhSize == 0) return;
-    // on a tile partition only the rays of this rank's tiles (tile t belongs to rank t % world)
-    if (pm.world > 1 && (((idx / cam.resx) / pm.tile) * pm.tilesX + (idx % cam.resx) / pm.tile) % pm.world != pm.rank) return;
-    Ray ray = gbufPrimaryRay(cam, idx % cam.resx, idx / cam.resx);
-    if (raySetAside(makeRaySlab(ray).cls)) {
-        const int at = atomicAdd(&pc->deferCount, 1);
-        if (at < kDeferCap) pc->deferred[at] = idx;
-    }
-}
-
-template <bool COUNT>
-__global__ __launch_bounds__(kWgTraceThreads) void k_gbuffer_literal(DScene s, DCamera cam, DCamera lastCam, GBufPtrs gb,
-                                                                      const PersistCounters *pc) {
-    __shared__ WgTraceShared sh;
-    const int n = pc->deferCount;
-    if (n > kDeferCap) return;  // k_gbuffer_persistent traces them all in place
-    for (int i = int(blockIdx.x); i < n; i += int(gridDim.x)) {
-        const int idx = pc->deferred[i];
-        Ray ray = gbufPrimaryRay(cam, idx % cam.resx, idx / cam.resx);
-        RaySlab rs = makeRaySlab(ray);
-        CoopTrace ct = wgTraceWhole<false>(s, s.nodes[getMTBVHId(-ray.d)], rs, 3.402823466e+38f, sh);
-        if (threadIdx.x == 0) {
-            gbufStore(s, cam, lastCam, gb, idx, rs, ct.hitPrim, ct.bary);
-            if (COUNT) {
-                atomicAdd(&s.counters->closestRays, 1ull);
-                atomicAdd(&s.counters->nodeVisits, (unsigned long long)ct.nodes);
-                atomicAdd(&s.counters->triTests, (unsigned long long)ct.tris);
-                if (ct.hitPrim != -1) atomicAdd(&s.counters->closestHits, 1ull);
-            }
-        }
-    }
 }
 
 }  // namespace rd

@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void k_gbuffer(DScene s, DCamera cam, DCamera 
             nHits++;
             Surface isec;
             fetchSurface(s, h.prim, h.bary, isec);
-            gb.motion[idx] = gbufMotionIndex(cam, lastCam, gb, isec, h.bary);  // first: see gbufStore (kernels_persist.h)
+            gb.motion[idx] = gbufMotionIndex(cam, lastCam, gb, isec, h.bary);  // first: see gbufStore (kernels_gbuffer.h)
             int matId = isec.matId;
             if (loadMaterial(s.mats, isec.matId).type == Light) matId = -2;  // NullPrimitive - 1 (:33-37, untextured record)
             Material material = texturedMaterial(s, isec);            // :44 (may perturb isec.norm)

@@ -1,15 +1,27 @@
-// radish_pt_amd/csrc/device/kernels_walk.h — a persistent WALK-ONLY kernel over a ray batch: box steps, leaf tests, retire, and
-// nothing else in its register allocation.
+// radish_pt_amd/csrc/device/kernels_walk.h — the WALK-ONLY kernels: box steps, leaf tests, retire, and nothing else in their
+// register allocation.  Three bodies, each written ONCE over a "work" type, and the ray-batch kernels around them; the G-buffer's
+// kernels around the same bodies are in kernels_gbuffer.h.
 //
-// k_trace_closest / k_trace_occluded (kernels_pt.h) give every ray a lane for the whole launch, so each wave waits for its
-// longest ray.  Here a lane whose ray has ended writes its record and takes the next ray of the batch (the lane-refill
-// structure of k_gbuffer_persistent, without a surface fetch).  DevScene::intersect (scene.h:262-301) /
-// DevScene::testOcclusion (:303-334) per lane, exactly as walkRay (traverse.h) performs them: same decisions, same counters.
-// Rays are handed out in chunks of 64 (the first chunk of a wave is its index, further ones come from an atomic counter).
-// The walker is ONE body, walkBatch<.., PAIRS>, with two entries: k_walk_persistent over the threaded arrays and k_walk_pair over
-// the sibling pairs.
+//   walkLanes    the lane-refill walker: a lane whose ray has ended writes its record and takes the next item.  Items are handed
+//                out in chunks of 64 (the first chunk of a wave is its index, further ones come from PersistCounters::blockHead).
+//                k_trace_closest / k_trace_occluded (kernels_pt.h) give every ray a lane for the whole launch, so each wave waits
+//                for its longest ray; here it does not.  DevScene::intersect (scene.h:262-301) / DevScene::testOcclusion
+//                (:303-334) per lane, exactly as walkRay (traverse.h) performs them: same decisions, same counters.
+//                Entries: k_walk_persistent (threaded arrays), k_walk_pair (sibling pairs), k_gbuffer_persistent.
+//   walkPacket   one 64-item chunk per wave, walked as a packet (traverse.h, packetWalk).  k_walk_packet, k_gbuffer_packet.
+//   wgTraceItem  one 1 024-thread workgroup per listed item (wg_trace.h).  k_trace_wg, k_trace_wg_list, k_gbuffer_literal.
+//
+// A work type is a plain struct that says where a lane's ray comes from and where its result goes; it remembers the item it
+// handed out (a ray index, a pixel index) itself:
+//   bool find(chunk, slot)    take the item in slot `slot` of chunk `chunk`; false: the slot holds none
+//   void findListed(entry)    take the item a list entry names
+//   Ray ray(float &tmax)      the ray of the item taken last, and how far it reaches
+//   void store(s, RaySlab, hitPrim, hitBary, tmax, found)   the record of that item's finished walk
+// BatchWork (below) is ray i of a float array with hits[i] / occluded[i]; PixelWork (kernels_gbuffer.h) is a pixel's centre ray
+// with its G-buffer record.
 #pragma once
 #include "kernels_persist.h"
+#include "wg_trace.h"
 
 namespace rd {
 
@@ -36,20 +48,49 @@ RD_DEV int4 hitRecord(int prim, v2 bary, float t) {
     return make_int4(prim, __float_as_int(hit ? bary.x : 0.f), __float_as_int(hit ? bary.y : 0.f), __float_as_int(hit ? t : 3.402823466e+38f));
 }
 
+// The work of the ray-batch kernels: ray i of `rays`, its record in hits[i] (closest) or occluded[i] (ANY).
+template <bool ANY>
+struct BatchWork {
+    const float *__restrict__ rays;
+    long long n;
+    int4 *__restrict__ hits;
+    int *__restrict__ occluded;
+    int slotList;
+    long long i;  // the ray taken last
+
+    RD_DEV bool find(long long chunk, int slot) {
+        const long long k = chunk * 64 + slot;
+        // slotList (ReSTIR's per-slot ray lists only): a NaN in the first float marks an EMPTY SLOT — no ray, no record,
+        // nothing counted (the consumer, k_restir_resolve, does not read the record of such a slot either).  The public
+        // ray-batch entries (rdh_trace_closest / rdh_trace_occluded) pass slotList = 0: a caller's ray with a NaN origin
+        // is a ray like any other (it fails the root's box test, as in DevScene::intersect) and is counted.
+        if (!(k < n && (slotList == 0 || rays[6 * k] == rays[6 * k]))) return false;
+        i = k;
+        return true;
+    }
+    RD_DEV void findListed(long long k) { i = k; }
+    RD_DEV Ray ray(float &tmax) const { return batchRay<ANY>(rays, i, tmax); }
+    RD_DEV void store(const DScene &, const RaySlab &, int hitPrim, v2 hitBary, float tmax, bool found) const {
+        if (ANY) occluded[i] = found ? 1 : 0;
+        else hits[i] = hitRecord(hitPrim, hitBary, tmax);
+    }
+};
+
 // DEFER (ReSTIR's ray lists): literal-class rays — one wave needs ~1 ms for one of them on the teapots scene, which is then the
 // duration of the whole launch — have been listed by the kernel that wrote the rays (at most kWalkDeferCap of them, else none is
 // set aside) and are traced by k_trace_wg_list, one 1 024-thread workgroup each, on a second stream beside this launch.
 constexpr int kWalkDeferCap = 256;
 
-// The lane-refill walker.  !PAIRS: a lane walks the threaded array of its ray's ordering (`nodes`, `node`; a finished walk stands
-// at `end`).  PAIRS: it walks the sibling pairs (DScene::pairs; traverse.h, pairStep) with the pair it enters next in `cur` and
-// its stack in `sp`: the wave's rows of LDS, `stk`, and behind them its strip of the overflow buffer, `ovf`.
-template <bool COUNT, bool ANY, bool DEFER, bool PAIRS>
-RD_DEV void walkBatch(const DScene &s, const float *__restrict__ rays, long long n, int4 *__restrict__ hits, int *__restrict__ occluded,
-                      PersistCounters *pc, const int *__restrict__ deferCount, int slotList, int2 *stk, int2 *ovf) {
+// The lane-refill walker over `chunks` chunks of 64 items.  !PAIRS: a lane walks the threaded array of its ray's ordering (`nodes`,
+// `node`; a finished walk stands at `end`).  PAIRS: it walks the sibling pairs (DScene::pairs; traverse.h, pairStep) with the pair
+// it enters next in `cur` and its stack in `sp`: the wave's rows of LDS, `stk`, and behind them its strip of the overflow buffer,
+// `ovf`.  deferAll (DEFER): literal-class items have been set aside for a workgroup-per-item launch; they are neither walked nor
+// counted here.  Idle lanes are refilled once REFILL_MIN of them wait, records written once FINISH_MIN 64ths of the busy lanes wait.
+// `work` is the caller's object, by reference: a copy of it as a by-value parameter changes the whole kernel's code.
+template <bool COUNT, bool ANY, bool DEFER, bool PAIRS, int REFILL_MIN, int FINISH_MIN, class Work>
+RD_DEV void walkLanes(const DScene &s, PersistCounters *pc, long long chunks, bool deferAll, int2 *stk, int2 *ovf, Work &work) {
     const int lane = int(threadIdx.x) & 63;
     const int end = s.bvhSize;
-    const long long chunks = (n + 63) / 64;
     WalkStats ws{0, 0};
     unsigned nRays = 0, nHits = 0;
     long long curChunk = (long long)blockIdx.x;
@@ -59,7 +100,6 @@ RD_DEV void walkBatch(const DScene &s, const float *__restrict__ rays, long long
 
     constexpr int W_IDLE = 0, W_TRACE = 1, W_DONE = 2;
     int state = W_IDLE;
-    long long rayIdx = 0;
     RaySlab rs;
     rs.o = rs.d = rs.inv = mk3(0.f);
     rs.cls = 0;
@@ -72,13 +112,12 @@ RD_DEV void walkBatch(const DScene &s, const float *__restrict__ rays, long long
     int hitPrim = -1;
     v2 hitBary = mk2(0.f, 0.f);
     bool found = false;
-    const bool deferAll = DEFER && *deferCount <= kWalkDeferCap;  // written by the kernel that produced the list, earlier in the stream
 
     for (;;) {
-        // ---------------- new rays for idle lanes ----------------
+        // ---------------- new items for idle lanes ----------------
         const unsigned long long idleM = __ballot(state == W_IDLE);
         const int nIdle = __popcll(idleM);
-        if (!exhausted && nIdle >= RD_WALK_REFILL_MIN) {
+        if (!exhausted && nIdle >= REFILL_MIN) {
             const int myRank = __popcll(idleM & laneMaskLt());
             int taken = 0;
             while (taken < nIdle && !exhausted) {
@@ -95,19 +134,13 @@ RD_DEV void walkBatch(const DScene &s, const float *__restrict__ rays, long long
                 const int avail = 64 - slotNext;
                 const int give = (nIdle - taken) < avail ? (nIdle - taken) : avail;
                 if (state == W_IDLE && myRank >= taken && myRank < taken + give) {
-                    const long long i = curChunk * 64 + slotNext + (myRank - taken);
-                    // slotList (ReSTIR's per-slot ray lists only): a NaN in the first float marks an EMPTY SLOT — no ray, no record,
-                    // nothing counted (the consumer, k_restir_resolve, does not read the record of such a slot either).  The public
-                    // ray-batch entries (rdh_trace_closest / rdh_trace_occluded) pass slotList = 0: a caller's ray with a NaN origin
-                    // is a ray like any other (it fails the root's box test, as in DevScene::intersect) and is counted.
-                    if (i < n && (slotList == 0 || rays[6 * i] == rays[6 * i])) {
-                        rayIdx = i;
-                        const Ray ray = batchRay<ANY>(rays, i, tmax);
+                    if (work.find(curChunk, slotNext + (myRank - taken))) {
+                        const Ray ray = work.ray(tmax);  // by value: filled through a reference it costs registers or time
                         rs = makeRaySlab(ray);
                         hitPrim = -1;
                         hitBary = mk2(0.f, 0.f);
                         found = false;
-                        if (!(DEFER && deferAll && raySetAside(rs.cls) && end != 0)) {  // else: k_trace_wg_list has this ray
+                        if (!(DEFER && deferAll && raySetAside(rs.cls) && end != 0)) {  // else: the workgroup-per-item launch has it
                             nRays++;
                             state = W_TRACE;
                             pending = -1;
@@ -219,17 +252,13 @@ RD_DEV void walkBatch(const DScene &s, const float *__restrict__ rays, long long
             pending = -1;
         }
         if (state == W_TRACE && pending < 0 && (PAIRS ? (cur == kPairNone && sp.sp == 0) : (node == end))) state = W_DONE;
-        // ---------------- records of finished rays ----------------
+        // ---------------- records of finished items ----------------
         const unsigned long long doneM = __ballot(state == W_DONE);
         const int nBusy = __popcll(__ballot(state != W_IDLE));
-        if (doneM != 0ull && __popcll(doneM) * 64 >= nBusy * RD_WALK_FINISH_MIN) {
+        if (doneM != 0ull && __popcll(doneM) * 64 >= nBusy * FINISH_MIN) {
             if (state == W_DONE) {
-                if (ANY) {
-                    occluded[rayIdx] = found ? 1 : 0;
-                } else {
-                    if (hitPrim != -1) nHits++;
-                    hits[rayIdx] = hitRecord(hitPrim, hitBary, tmax);
-                }
+                if (!ANY && hitPrim != -1) nHits++;
+                work.store(s, rs, hitPrim, hitBary, tmax, found);
                 state = W_IDLE;
             }
         }
@@ -241,7 +270,9 @@ template <bool COUNT, bool ANY, bool DEFER = false>
 __global__ __launch_bounds__(64) void k_walk_persistent(DScene s, const float *__restrict__ rays, long long n, int4 *__restrict__ hits,
                                                         int *__restrict__ occluded, PersistCounters *pc,
                                                         const int *__restrict__ deferCount = nullptr, int slotList = 0) {
-    walkBatch<COUNT, ANY, DEFER, false>(s, rays, n, hits, occluded, pc, deferCount, slotList, nullptr, nullptr);
+    const bool deferAll = DEFER && *deferCount <= kWalkDeferCap;  // written by the kernel that produced the list, earlier in the stream
+    BatchWork<ANY> work{rays, n, hits, occluded, slotList, 0};
+    walkLanes<COUNT, ANY, DEFER, false, RD_WALK_REFILL_MIN, RD_WALK_FINISH_MIN>(s, pc, (n + 63) / 64, deferAll, nullptr, nullptr, work);
 }
 
 template <bool COUNT, bool ANY, bool DEFER = false>
@@ -250,32 +281,32 @@ __global__ __launch_bounds__(64, COUNT ? 1 : 7) void k_walk_pair(DScene s, const
                                                   int overflowDepth, const int *__restrict__ deferCount = nullptr, int slotList = 0) {
     __shared__ int2 stk[kPairLds * 64];
     int2 *const ovf = overflow + (size_t)blockIdx.x * (size_t)overflowDepth * 64;
-    walkBatch<COUNT, ANY, DEFER, true>(s, rays, n, hits, occluded, pc, deferCount, slotList, stk, ovf);
+    const bool deferAll = DEFER && *deferCount <= kWalkDeferCap;
+    BatchWork<ANY> work{rays, n, hits, occluded, slotList, 0};
+    walkLanes<COUNT, ANY, DEFER, true, RD_WALK_REFILL_MIN, RD_WALK_FINISH_MIN>(s, pc, (n + 63) / 64, deferAll, stk, ovf, work);
 }
 
-// ---- closest hits of a COHERENT ray list — consecutive rays start side by side, e.g. the primary rays of 8x8 pixel blocks in slot
-// order — one 64-ray chunk per wave, walked as a PACKET (traverse.h, packetWalk): one uniform node load per visit for the whole wave
+// ---- closest hits of a COHERENT chunk — consecutive items start side by side, e.g. the primary rays of an 8x8 pixel block in slot
+// order — by one wave, walked as a PACKET (traverse.h, packetWalk): one uniform node load per visit for the whole wave
 // instead of one L1 request per lane.  Same records, same counters as the lane-refill walkers; on rays that do not travel together
 // it is merely slow (a wave then visits the union of 64 unrelated walks), so the caller says when a list is coherent.
-// Literal-class rays: set aside for k_trace_wg_list when the producer listed them (DEFER), else traced whole by the wave, in place.
-template <bool COUNT, bool DEFER>
-__global__ __launch_bounds__(256) void k_walk_packet(DScene s, const float *__restrict__ rays, long long n, int4 *__restrict__ hits,
-                                                     const int *__restrict__ deferCount, int slotList, int budget) {
+// Literal-class rays: set aside for the workgroup-per-item launch when they were listed (deferAll), else traced whole by the wave,
+// in place, one after the other.
+template <bool COUNT, bool DEFER, class Work>
+RD_DEV void walkPacket(const DScene &s, long long chunk, bool deferAll, int budget, Work &work) {
     const int lane = int(threadIdx.x) & 63;
-    const long long i = ((long long)blockIdx.x * 4 + (long long)(threadIdx.x >> 6)) * 64 + lane;
     const int end = s.bvhSize;
     WalkStats ws{0, 0};
     unsigned nRays = 0, nHits = 0;
-    const bool deferAll = DEFER && *deferCount <= kWalkDeferCap;
-    const bool have = i < n && (slotList == 0 || rays[6 * i] == rays[6 * i]);  // see walkBatch
     Ray ray{mk3(0.f), mk3(0.f, 0.f, 1.f)};
     float tmax = 3.402823466e+38f;
-    if (have) ray = batchRay<false>(rays, i, tmax);
+    const bool have = work.find(chunk, lane);
+    if (have) ray = work.ray(tmax);
     const RaySlab rs = makeRaySlab(ray);
     const int ord = getMTBVHId(-ray.d);
     int hitPrim = -1;
     v2 hitBary = mk2(0.f, 0.f);
-    const bool traced = have && !(DEFER && deferAll && raySetAside(rs.cls) && end != 0);  // else: k_trace_wg_list has this ray
+    const bool traced = have && !(DEFER && deferAll && raySetAside(rs.cls) && end != 0);
     if (traced) nRays++;
     unsigned long long lit = __ballot(traced && rs.cls != 0 && end != 0);
     while (lit) {
@@ -296,24 +327,31 @@ __global__ __launch_bounds__(256) void k_walk_packet(DScene s, const float *__re
     packetWalkAll<COUNT>(s, traced && rs.cls == 0 && end != 0, ord, rs, tmax, hitPrim, hitBary, ws, budget);
     if (traced) {
         if (hitPrim != -1) nHits++;
-        hits[i] = hitRecord(hitPrim, hitBary, tmax);
+        work.store(s, rs, hitPrim, hitBary, tmax, false);
     }
     if (COUNT) flushCounters(s.counters, nRays, 0u, nHits, ws);
 }
 
-// One WORKGROUP per ray (wg_trace.h) over a ray batch: RDH_PT_WG_PER_RAY on the ray-batch entries.  This is how the G-buffer
-// traces its literal-class rays; as an entry of its own it lets the tests put every kind of ray
-// through wgTraceWhole (closest and any-hit) and compare records and counters with the oracle.  Far slower than the walkers
-// for ordinary rays: 16 waves per ray.
-template <bool COUNT, bool ANY>
-RD_DEV void wgTraceRay(const DScene &s, const float *__restrict__ rays, long long i, int4 *__restrict__ hits, int *__restrict__ occluded,
-                       WgTraceShared &sh) {
+template <bool COUNT, bool DEFER>
+__global__ __launch_bounds__(256) void k_walk_packet(DScene s, const float *__restrict__ rays, long long n, int4 *__restrict__ hits,
+                                                     const int *__restrict__ deferCount, int slotList, int budget) {
+    const bool deferAll = DEFER && *deferCount <= kWalkDeferCap;
+    BatchWork<false> work{rays, n, hits, nullptr, slotList, 0};
+    walkPacket<COUNT, DEFER>(s, (long long)blockIdx.x * 4 + (long long)(threadIdx.x >> 6), deferAll, budget, work);
+}
+
+// One WORKGROUP per item (wg_trace.h): how the G-buffer and ReSTIR trace the literal-class rays they set aside, and, over a whole
+// ray batch (RDH_PT_WG_PER_RAY on the ray-batch entries), how the tests put every kind of ray through wgTraceWhole (closest and
+// any-hit) and compare records and counters with the oracle.  Far slower than the walkers for ordinary rays: 16 waves per ray.
+template <bool COUNT, bool ANY, class Work, class Entry>
+RD_DEV void wgTraceItem(const DScene &s, Entry entry, WgTraceShared &sh, Work work) {
     float tmax;
-    const Ray ray = batchRay<ANY>(rays, i, tmax);
-    CoopTrace ct = wgTraceWhole<ANY>(s, s.nodes[getMTBVHId(-ray.d)], makeRaySlab(ray), tmax, sh);
+    work.findListed(entry);
+    const Ray ray = work.ray(tmax);
+    const RaySlab rs = makeRaySlab(ray);
+    CoopTrace ct = wgTraceWhole<ANY>(s, s.nodes[getMTBVHId(-ray.d)], rs, tmax, sh);
     if (threadIdx.x == 0) {
-        if (ANY) occluded[i] = ct.found ? 1 : 0;
-        else hits[i] = hitRecord(ct.hitPrim, ct.bary, ct.tmax);
+        work.store(s, rs, ct.hitPrim, ct.bary, ct.tmax, ct.found);
         if (COUNT) {
             atomicAdd(ANY ? &s.counters->anyRays : &s.counters->closestRays, 1ull);
             atomicAdd(&s.counters->nodeVisits, (unsigned long long)ct.nodes);
@@ -327,7 +365,8 @@ template <bool COUNT, bool ANY>
 __global__ __launch_bounds__(kWgTraceThreads) void k_trace_wg(DScene s, const float *__restrict__ rays, long long n, int4 *__restrict__ hits,
                                                               int *__restrict__ occluded) {
     __shared__ WgTraceShared sh;
-    for (long long i = (long long)blockIdx.x; i < n; i += (long long)gridDim.x) wgTraceRay<COUNT, ANY>(s, rays, i, hits, occluded, sh);
+    const BatchWork<ANY> work{rays, n, hits, occluded, 0, 0};
+    for (long long i = (long long)blockIdx.x; i < n; i += (long long)gridDim.x) wgTraceItem<COUNT, ANY>(s, i, sh, work);
 }
 
 // k_trace_wg over an index list (the literal-class rays a producer kernel set aside): list[0 .. *count) are indices into `rays`.
@@ -338,6 +377,7 @@ __global__ __launch_bounds__(kWgTraceThreads) void k_trace_wg_list(DScene s, con
     __shared__ WgTraceShared sh;
     const int n = *count;
     if (n > kWalkDeferCap) return;  // the walker traces them all in place
-    for (int k = int(blockIdx.x); k < n; k += int(gridDim.x)) wgTraceRay<COUNT, ANY>(s, rays, list[k], hits, occluded, sh);
+    const BatchWork<ANY> work{rays, 0, hits, occluded, 0, 0};
+    for (int k = int(blockIdx.x); k < n; k += int(gridDim.x)) wgTraceItem<COUNT, ANY>(s, (long long)list[k], sh, work);
 }
 }  // namespace rd

@@ -27,6 +27,7 @@
 #include "device/kernels_wave.h"
 #include "device/kernels_persist.h"
 #include "device/kernels_walk.h"
+#include "device/kernels_gbuffer.h"
 #include "device/kernels_display.h"
 #include "device/kernels_denoise.h"
 #include "device/kernels_bvh.h"
@@ -1719,7 +1720,7 @@ static int enqueueGBuffer(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
     timeBegin(c);
     HIP_TRY(c, hipMemsetAsync(c->dPersist, 0, offsetof(PersistCounters, deferred), c->stream));
     // literal-class rays are listed first and traced on a second stream beside the rest, each by a whole workgroup
-    // (kernels_persist.h, k_gbuffer_literal): traced in place, ONE such ray (1.2 ms on the teapots scene) was the duration of
+    // (kernels_gbuffer.h, k_gbuffer_literal): traced in place, ONE such ray (1.2 ms on the teapots scene) was the duration of
     // the pass.  RDH_PT_NO_DEFER keeps them in the persistent kernel.
     const bool defer = !(flags & RDH_PT_NO_DEFER);
     if (defer) {
@@ -1730,7 +1731,7 @@ static int enqueueGBuffer(rdh_ctx *c, const rdh_gbuffer *gb, uint32_t flags) {
             hipLaunchKernelGGL(k_gbuffer_literal<cnt.value>, dim3(kDeferCap), dim3(kWgTraceThreads), 0, c->litStream, c->scene.ds, c->cam, last, p, c->dPersist);
         }, count);
     }
-    if (usePackets(flags)) {  // one 8x8 block per wave, its 64 centre rays walked as a packet (kernels_persist.h, k_gbuffer_packet)
+    if (usePackets(flags)) {  // one 8x8 block per wave, its 64 centre rays walked as a packet (kernels_gbuffer.h, k_gbuffer_packet)
         const unsigned pgrid = ((unsigned)pm.numBlocks + 3u) / 4u;
         withBools([&](auto cnt, auto def) {
             hipLaunchKernelGGL((k_gbuffer_packet<cnt.value, def.value>), dim3(pgrid), dim3(256), 0, c->stream, c->scene.ds, c->cam, last, pm, p, c->dPersist,

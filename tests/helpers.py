@@ -44,6 +44,40 @@ def assert_bit_equal(a, b, what=""):
         )
 
 
+def chain_scene(n_stack):
+    """n_stack coincident triangles with alternating materials over a floor, under a lamp: the SAH builder has nothing to split on
+    and returns a CHAIN (one leaf and one inner child per level), and every ray that hits one of the triangles hits all of them at
+    the same distance."""
+    from radish_pt_amd import layouts as L, scenes
+
+    mats = [L.make_material(L.LAMBERTIAN, (0.8, 0.3, 0.2)), L.make_material(L.LAMBERTIAN, (0.2, 0.7, 0.9)),
+            L.make_material(L.METALLIC_WORKFLOW, (0.9, 0.9, 0.9), metallic=0.6, roughness=0.35), L.make_material(L.LIGHT, (7.0, 6.5, 6.0))]
+    tri = np.array([[-1.2, -0.4, 0.1], [1.3, -0.5, -0.2], [0.1, 1.4, 0.3]], np.float32)
+    nrm = np.cross(tri[1] - tri[0], tri[2] - tri[0])
+    nrm = np.tile((nrm / np.linalg.norm(nrm)).astype(np.float32), (3, 1))
+    uv = np.array([[0, 0], [1, 0], [0, 1]], np.float32)
+    floor = np.array([[-3, -0.8, -3], [3, -0.8, -3], [3, -0.8, 3], [-3, -0.8, -3], [3, -0.8, 3], [-3, -0.8, 3]], np.float32)
+    lamp = np.array([[-0.6, 2.4, -0.6], [0.6, 2.4, -0.6], [0.6, 2.4, 0.6], [-0.6, 2.4, -0.6], [0.6, 2.4, 0.6], [-0.6, 2.4, 0.6]], np.float32)  # facing down
+    v = np.concatenate([np.tile(tri, (n_stack, 1)), floor, lamp])
+    n = np.concatenate([np.tile(nrm, (n_stack, 1)), np.tile(np.array([0, 1, 0], np.float32), (6, 1)), np.tile(np.array([0, -1, 0], np.float32), (6, 1))])
+    t = np.tile(uv, (n_stack + 4, 1))
+    ids = np.array([i % 3 for i in range(n_stack)] + [0, 0, 3, 3], np.int32)
+    return scenes.SceneData(f"chain{n_stack}", v, n, t, ids, np.array(mats, dtype=L.MATERIAL_DTYPE))
+
+
+def count_literal_primary_rays(cam):
+    """How many un-jittered centre rays of `cam` have a direction component below the box test's Eps (bvh.h:138-148)."""
+    W, H = int(cam["resolution"][0]), int(cam["resolution"][1])
+    x, y = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    ru = 1.0 - (x + 0.5) / W * 2.0
+    rv = 1.0 - (y + 0.5) / H * 2.0
+    t = float(cam["tanFovY"])
+    d = (ru * (W / H) * t)[..., None] * cam["right"].astype(np.float64) + (rv * t)[..., None] * cam["up"].astype(np.float64) \
+        + cam["view"].astype(np.float64)
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    return int((np.abs(d) < 5e-7).any(axis=-1).sum())
+
+
 def restir_partition_run(gpu_ctx, sd, W, H, cams, world, tile, reuse):
     """ReSTIR frames on `world` virtual ranks (one rdh_ctx each, all on this GPU): whole-frame G-buffer, rdh_restir_direct per
     rank into its packed tiles, reservoir exchange (pack -> simulated all-gather -> unpack), rdh_untile.  Returns the frames and

@@ -1,7 +1,7 @@
 """numpy float32 restatement of the G-buffer's motion plane (rdh_gbuffer_render with rdh_scene_track_motion), shared
 by test_motion_model_cpu.py and test_gpu_motion.py.
 
-Operation for operation what the kernels do: gbufPrimaryRay (kernels_persist.h), the position interpolation of fetchSurface
+Operation for operation what the kernels do: gbufPrimaryRay (kernels_gbuffer.h), the position interpolation of fetchSurface
 (lights.h), cameraRasterUV (bsdf.h) and the index rule of gbufMotionIndex (kernels_pt.h).  numpy's float32 add / sub / mul / div /
 sqrt are IEEE binary32 operations and are never contracted, which is the library's numerics contract.  The one libm
 call is the host's tanf in toDeviceCamera (radish_hip.hip); it is taken from the same libm, since np.tan need not round alike.

@@ -8,7 +8,8 @@ of every bit.  Each test also reports the fraction of pixels outside 1e-4 relati
 import numpy as np
 import pytest
 
-from helpers import assert_bit_equal, random_rays, random_segments, restir_partition_run as _restir_partition_run
+from helpers import (assert_bit_equal, chain_scene, count_literal_primary_rays as _count_literal_primary_rays, random_rays,
+                     random_segments, restir_partition_run as _restir_partition_run)
 
 pytestmark = pytest.mark.gpu
 
@@ -480,19 +481,6 @@ def test_gbuffer_kernels_bit_exact(gpu_ctx, kernel):
         gb_ref.update(cam)
         gb.update(cam)
     assert (gb_ref.primId[0] >= 0).mean() > 0.3
-
-
-def _count_literal_primary_rays(cam):
-    """How many un-jittered centre rays of `cam` have a direction component below the box test's Eps (bvh.h:138-148)."""
-    W, H = int(cam["resolution"][0]), int(cam["resolution"][1])
-    x, y = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
-    ru = 1.0 - (x + 0.5) / W * 2.0
-    rv = 1.0 - (y + 0.5) / H * 2.0
-    t = float(cam["tanFovY"])
-    d = (ru * (W / H) * t)[..., None] * cam["right"].astype(np.float64) + (rv * t)[..., None] * cam["up"].astype(np.float64) \
-        + cam["view"].astype(np.float64)
-    d /= np.linalg.norm(d, axis=-1, keepdims=True)
-    return int((np.abs(d) < 5e-7).any(axis=-1).sum())
 
 
 @pytest.mark.parametrize("size", [(151, 91), (301, 45)])
@@ -1022,22 +1010,10 @@ def test_chain_shaped_tree_ties_deep_stacks_and_the_threaded_fallback(gpu_ctx, n
     (failed far children are stacked too) — an LDS ring of 8 entries, the rest in the global strip (traverse.h, pairPush).  2 300
     levels is past the depth the strips are sized for (radish_hip.hip, kMaxPairDepth): the scene silently keeps the threaded walk,
     and asking for pairs by flag is refused.  Either way: hits, images and work counters equal the oracle's."""
-    from radish_pt_amd import api, hostlib, layouts as L, scenes
+    from radish_pt_amd import api, hostlib, layouts as L
 
     torch = _torch()
-    mats = [L.make_material(L.LAMBERTIAN, (0.8, 0.3, 0.2)), L.make_material(L.LAMBERTIAN, (0.2, 0.7, 0.9)),
-            L.make_material(L.METALLIC_WORKFLOW, (0.9, 0.9, 0.9), metallic=0.6, roughness=0.35), L.make_material(L.LIGHT, (7.0, 6.5, 6.0))]
-    tri = np.array([[-1.2, -0.4, 0.1], [1.3, -0.5, -0.2], [0.1, 1.4, 0.3]], np.float32)
-    nrm = np.cross(tri[1] - tri[0], tri[2] - tri[0])
-    nrm = np.tile((nrm / np.linalg.norm(nrm)).astype(np.float32), (3, 1))
-    uv = np.array([[0, 0], [1, 0], [0, 1]], np.float32)
-    floor = np.array([[-3, -0.8, -3], [3, -0.8, -3], [3, -0.8, 3], [-3, -0.8, -3], [3, -0.8, 3], [-3, -0.8, 3]], np.float32)
-    lamp = np.array([[-0.6, 2.4, -0.6], [0.6, 2.4, -0.6], [0.6, 2.4, 0.6], [-0.6, 2.4, -0.6], [0.6, 2.4, 0.6], [-0.6, 2.4, 0.6]], np.float32)  # facing down
-    v = np.concatenate([np.tile(tri, (n_stack, 1)), floor, lamp])
-    n = np.concatenate([np.tile(nrm, (n_stack, 1)), np.tile(np.array([0, 1, 0], np.float32), (6, 1)), np.tile(np.array([0, -1, 0], np.float32), (6, 1))])
-    t = np.tile(uv, (n_stack + 4, 1))
-    ids = np.array([i % 3 for i in range(n_stack)] + [0, 0, 3, 3], np.int32)
-    sd = scenes.SceneData(f"chain{n_stack}", v, n, t, ids, np.array(mats, dtype=L.MATERIAL_DTYPE))
+    sd = chain_scene(n_stack)
     gpu_ctx.set_partition(0, 1, 64)
     gpu_ctx.upload_scene(sd)
     o = _oracle(sd)

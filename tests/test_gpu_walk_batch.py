@@ -1,4 +1,4 @@
-"""The ray-batch walkers (kernels_walk.h: walkBatch behind k_walk_persistent and k_walk_pair) with MORE WORK THAN WAVES.
+"""The ray-batch walkers (kernels_walk.h: walkLanes behind k_walk_persistent and k_walk_pair) with MORE WORK THAN WAVES.
 
 The other ray-batch tests trace 4 096 or 8 192 rays: the launch is then never larger than the work, every wave gets exactly the one
 64-ray chunk of its index, and neither the shared chunk head (PersistCounters::blockHead) nor a refill that crosses a chunk
