@@ -623,6 +623,28 @@ int rdh_debug_persist_stamps(rdh_ctx *ctx, uint64_t *out5x4096);
  * wave-steps, [9] box lane-steps, [10] leaf calls, [11] leaf lanes, [12] shade calls, [13] shade lanes, [14] raygen calls,
  * [15] raygen lanes.  RDH_ERR_UNSUPPORTED otherwise. */
 int rdh_debug_persist_phases(rdh_ctx *ctx, uint64_t *out16);
+/* Test access to the persistent path tracer's block scheduler (k_persist_schedule and the launch sequence rdh_path_trace keeps
+ * around it with RDH_PT_PERSISTENT).
+ * rdh_debug_persist_schedule: the schedule kernel alone, one launch on the context's stream over the CALLER's device arrays:
+ * d_cost and d_ema (n words each, read and written: the costs are folded into the running means and zeroed) and d_order (n words,
+ * written: the blocks in descending quarter-octave bucket of their new mean).  Nothing beyond word n - 1 of any array is touched.
+ * Asynchronous; needs no scene and no camera.  A null pointer or n < 1: RDH_ERR_ARGS.
+ * rdh_debug_persist_read: the sequence's state.  Blocking: waits for the context's stream and its side stream.  Returns the block
+ * count B the arrays are sized for (0 before the first persistent launch) or a negative RDH_ERR_*.  state4 (may be NULL):
+ * {persistent launches since the last restart, 1 while the sequence is valid (0: the next launch restarts it), B, the block count of
+ * a pending rdh_debug_persist_set_order or 0}.  When capacity >= B > 0, each array that is not NULL is filled: orders = both
+ * blockOrder buffers, 2 * B words (buffer 0, then buffer 1; a buffer no schedule has written yet holds whatever the allocation
+ * held), costs = both blockCost buffers alike, ema = the B running means.  Launch n of a sequence writes costs to buffer n & 1;
+ * its schedule writes order buffer n & 1, which launch n + 2 reads.
+ * rdh_debug_persist_set_order: the NEXT persistent launch of this context, and only that one, visits its blocks in the order of
+ * the HOST array `order`, whatever its place in the sequence and with or without RDH_PT_NO_SCHEDULE.  Costs, running means, the
+ * schedule kernel and the launch count go on as they would have.  `order` must be a permutation of 0 .. n - 1 and n the block
+ * count of the current camera and partition; otherwise RDH_ERR_ARGS and nothing changes (RDH_ERR_NO_SCENE without a camera).
+ * Whatever restarts the sequence (a new scene or tree, another resolution, partition, stream or occupancy share) drops a pending
+ * order.  Blocking (waits for the context's stream). */
+int rdh_debug_persist_schedule(rdh_ctx *ctx, uint32_t *d_cost, uint32_t *d_ema, int32_t *d_order, int32_t n);
+int rdh_debug_persist_read(rdh_ctx *ctx, int32_t *state4, int32_t *orders, uint32_t *costs, uint32_t *ema, int32_t capacity);
+int rdh_debug_persist_set_order(rdh_ctx *ctx, const int32_t *order, int32_t n);
 /* Diagnostic builds only (-DRD_WF_STAMPS): wall-clock stamps (100 MHz ticks) of the trace stages of the last wavefront pass
  * (its first pipeline), out[(stage * waves + logical wave) * 3 + i] — i = 0 the wave entered k_wf_trace, 1 it first found the
  * stage's queue exhausted, 2 it left; 0 where a wave wrote none.  *stages and *waves are always set; the stamps are copied when

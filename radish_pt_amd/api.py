@@ -78,6 +78,7 @@ EXPORTS = [
     "rdh_scene_set_texture", "rdh_scene_env_power", "rdh_debug_read_textures",
     "rdh_scene_set_geometry", "rdh_debug_read_geometry",
     "rdh_path_trace_adaptive", "rdh_adaptive_plan",
+    "rdh_debug_persist_schedule", "rdh_debug_persist_read", "rdh_debug_persist_set_order",
 ]
 
 
@@ -240,6 +241,17 @@ def adaptive_entries():
     trace.argtypes, trace.restype = [vp, vp, vp, vp, vp, vp, i32, i32, C.c_uint32, C.POINTER(C.c_int64)], i32
     plan.argtypes, plan.restype = [vp, vp, vp, vp, i32, i32, i32, C.c_float, C.POINTER(AdaptiveStatsC)], i32
     return trace, plan
+
+
+def persist_entries():
+    """(rdh_debug_persist_schedule, rdh_debug_persist_read, rdh_debug_persist_set_order) with their signatures; bound at first use
+    for the same reason as adaptive_entries."""
+    vp, i32 = C.c_void_p, C.c_int32
+    sched, read, set_order = lib().rdh_debug_persist_schedule, lib().rdh_debug_persist_read, lib().rdh_debug_persist_set_order
+    sched.argtypes, sched.restype = [vp, vp, vp, vp, i32], i32
+    read.argtypes, read.restype = [vp, vp, vp, vp, vp, i32], i32
+    set_order.argtypes, set_order.restype = [vp, vp, i32], i32
+    return sched, read, set_order
 
 
 class RadishError(RuntimeError):
@@ -975,6 +987,38 @@ class Context:
         out = np.zeros((5, 4096), dtype=np.uint64)
         self.check(lib().rdh_debug_persist_stamps(self.h, out.ctypes.data))
         return out
+
+    def debug_persist_schedule(self, cost, ema, order, n):
+        """k_persist_schedule alone over the caller's arrays (rdh_debug_persist_schedule): cost / ema / order are int32 cuda tensors
+        holding the kernel's 32-bit words (torch has no unsigned 32-bit arithmetic; view them), at least n each.  Asynchronous."""
+        torch = _torch()
+        n = int(n)
+        ptrs = [self._ptr(t, max(n, 1), f"debug_persist_schedule {name}", torch.int32) for t, name in ((cost, "cost"), (ema, "ema"), (order, "order"))]
+        self.check(persist_entries()[0](self.h, *ptrs, n))
+
+    def debug_persist_read(self):
+        """The block-order sequence as it stands (rdh_debug_persist_read; blocking): a dict of frame (persistent launches since the
+        last restart), valid, blocks, pending (block count of an order set with debug_persist_set_order, or 0), orders int32
+        [2, blocks], costs uint32 [2, blocks], ema uint32 [blocks]."""
+        read = persist_entries()[1]
+        state = np.zeros(4, np.int32)
+        n = read(self.h, state.ctypes.data, None, None, None, 0)
+        if n < 0:
+            self.check(n)
+        orders, costs, ema = np.zeros((2, n), np.int32), np.zeros((2, n), np.uint32), np.zeros(n, np.uint32)
+        if n:
+            rc = read(self.h, state.ctypes.data, orders.ctypes.data, costs.ctypes.data, ema.ctypes.data, n)
+            if rc < 0:
+                self.check(rc)
+            assert rc == n
+        return {"frame": int(state[0]), "valid": bool(state[1]), "blocks": int(state[2]), "pending": int(state[3]),
+                "orders": orders, "costs": costs, "ema": ema}
+
+    def debug_persist_set_order(self, order):
+        """The next persistent launch, and only that one, visits its blocks in `order` (rdh_debug_persist_set_order): a permutation
+        of range(blocks of the current camera and partition).  Raises on anything else, nothing changed."""
+        order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        self.check(persist_entries()[2](self.h, order.ctypes.data if len(order) else None, len(order)))
 
     def debug_wf_stamps(self):
         """uint64 [stages, waves, 6] of the last wavefront pass's trace stages: entry, queue dry, exit, list loop left (100 MHz

@@ -205,6 +205,10 @@ struct rdh_ctx {
     bool orderValid = false;        // false: restart the sequence (scene, camera size or partition changed)
     int persistFrame = 0;           // persistent launches since the last restart
     hipEvent_t evFrame = nullptr, evSched[2] = {nullptr, nullptr};
+    // rdh_debug_persist_set_order: a caller's permutation for the next persistent launch only (a buffer of its own: the schedule
+    // kernel never sees it).  Whatever restarts the sequence drops it (restartSchedule).
+    GrowBuf testOrder{bufs};        // blocks (int)
+    int testOrderBlocks = 0;        // > 0: an order of that many blocks is pending
 
     // camera
     bool haveCamera = false;
@@ -298,6 +302,12 @@ namespace {
 
 int waitExchanges(rdh_ctx *c, bool gbuf, bool resv);  // defined with the collectives below
 int joinComm(rdh_ctx *c);
+
+// The persistent launches' block-order sequence starts again with the next one: two launches in plain order (rdh_path_trace).
+void restartSchedule(rdh_ctx *c) {
+    c->orderValid = false;
+    c->testOrderBlocks = 0;
+}
 
 int fail(rdh_ctx *c, int code, const char *fmt, ...) {
     char buf[512];
@@ -1168,7 +1178,7 @@ int rdh_set_stream(rdh_ctx *c, void *s) {
         if (c->wfStream) HIP_TRY(c, hipStreamSynchronize(c->wfStream));
         if (c->commStream) HIP_TRY(c, hipStreamSynchronize(c->commStream));
         c->gbufPending = c->resvPending = false;
-        c->orderValid = false;
+        restartSchedule(c);
         c->stream = ns;
     }
     return RDH_OK;
@@ -1374,7 +1384,7 @@ int rdh_scene_upload(rdh_ctx *c, const rdh_scene_desc *d) {
     c->scene.texInfo.assign(texInfo.begin(), texInfo.begin() + d->numTextures);  // rdh_scene_set_texture checks sizes against these
     c->scene.texFloats = texFloats;
     c->scene.haveScene = true;
-    c->orderValid = false;
+    restartSchedule(c);
     return RDH_OK;
 }
 
@@ -1382,7 +1392,7 @@ int rdh_set_camera(rdh_ctx *c, const void *camera196) {
     if (!c || !camera196) return RDH_ERR_ARGS;
     DCamera d = toDeviceCamera(camera196);
     if (d.resx <= 0 || d.resy <= 0) return fail(c, RDH_ERR_ARGS, "camera resolution %dx%d", d.resx, d.resy);
-    if (d.resx != c->cam.resx || d.resy != c->cam.resy) c->orderValid = false;
+    if (d.resx != c->cam.resx || d.resy != c->cam.resy) restartSchedule(c);
     c->cam = d;
     c->haveCamera = true;
     return RDH_OK;
@@ -1391,7 +1401,7 @@ int rdh_set_camera(rdh_ctx *c, const void *camera196) {
 int rdh_set_partition(rdh_ctx *c, int rank, int world, int tileSize) {
     if (!c || world < 1 || rank < 0 || rank >= world || tileSize < 8 || (tileSize % 8) != 0)
         return fail(c, RDH_ERR_ARGS, "rdh_set_partition(rank=%d, world=%d, tile=%d)", rank, world, tileSize);
-    if (rank != c->rank || world != c->world || tileSize != c->tile) c->orderValid = false;
+    if (rank != c->rank || world != c->world || tileSize != c->tile) restartSchedule(c);
     c->rank = rank;
     c->world = world;
     c->tile = tileSize;
@@ -1454,7 +1464,6 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
                 b->release();  // sized for this frame, also when it has fewer blocks than the last (both streams are idle)
                 if ((rc = grow(c, *b, (size_t)pm.numBlocks, sizeof(unsigned) * (size_t)pm.numBlocks, Busy::Nothing))) return rc;
             }
-            HIP_TRY(c, hipMemsetAsync(c->blockEma.p, 0, sizeof(unsigned) * (size_t)pm.numBlocks, c->stream));
             c->costBlocks = pm.numBlocks;
             c->orderValid = false;
         }
@@ -1462,6 +1471,9 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
             HIP_TRY(c, hipStreamSynchronize(c->sideStream));
             for (int k = 0; k < 2; k++)
                 HIP_TRY(c, hipMemsetAsync(c->blockCost[k].p, 0, sizeof(unsigned) * (size_t)pm.numBlocks, c->stream));
+            // ... and no means: block b of the old scene, camera or partition looked at something else (kept, they would be folded
+            // 7 : 1 into the new ones, and blocks that hold no pixel now would be ordered by what their namesakes cost)
+            HIP_TRY(c, hipMemsetAsync(c->blockEma.p, 0, sizeof(unsigned) * (size_t)pm.numBlocks, c->stream));
             c->persistFrame = 0;
             c->orderValid = true;
         }
@@ -1473,6 +1485,8 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
         const bool useOrder = n >= 2 && !(flags & RDH_PT_NO_SCHEDULE);
         HIP_TRY(c, hipMemsetAsync(c->dPersist, 0, offsetof(PersistCounters, deferred), c->stream));
         const int *order = useOrder ? c->blockOrder[cb].as<int>() : nullptr;
+        if (c->testOrderBlocks == pm.numBlocks) order = c->testOrder.as<int>();  // rdh_debug_persist_set_order: this launch only
+        c->testOrderBlocks = 0;
         long pp = profBegin(c, flags);
         int2 *const ovf = pairs ? c->treeOvf.as<int2>() : nullptr;
         withBools([&](auto cnt, auto pr) {
@@ -2544,7 +2558,7 @@ int rdh_dump_rays(rdh_ctx *c, int looper, int maxDepth, float *d_closest, int64_
 
 int rdh_set_occupancy_share(rdh_ctx *c, int share) {
     if (!c || share < 1 || share > 64) return c ? fail(c, RDH_ERR_ARGS, "rdh_set_occupancy_share(%d)", share) : RDH_ERR_ARGS;
-    if (share != c->share) c->orderValid = false;
+    if (share != c->share) restartSchedule(c);
     c->share = share;
     return RDH_OK;
 }
@@ -2598,6 +2612,58 @@ int rdh_debug_persist_stamps(rdh_ctx *c, uint64_t *out5x4096) {
 #else
     return fail(c, RDH_ERR_UNSUPPORTED, "library built without RD_PERSIST_STAMPS");
 #endif
+}
+
+int rdh_debug_persist_schedule(rdh_ctx *c, uint32_t *d_cost, uint32_t *d_ema, int32_t *d_order, int32_t n) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!d_cost || !d_ema || !d_order || n < 1) return fail(c, RDH_ERR_ARGS, "rdh_debug_persist_schedule: null array or n = %d", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_persist_schedule, dim3(1), dim3(kScheduleThreads), 0, c->stream, d_cost, d_ema, d_order, n);
+    HIP_TRY(c, hipGetLastError());
+    return RDH_OK;
+}
+
+int rdh_debug_persist_read(rdh_ctx *c, int32_t *state4, int32_t *orders, uint32_t *costs, uint32_t *ema, int32_t capacity) {
+    if (!c || capacity < 0) return RDH_ERR_ARGS;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->sideStream) HIP_TRY(c, hipStreamSynchronize(c->sideStream));
+    const int n = c->costBlocks;
+    if (state4) {
+        state4[0] = c->persistFrame;
+        state4[1] = c->orderValid ? 1 : 0;
+        state4[2] = n;
+        state4[3] = c->testOrderBlocks;
+    }
+    if (n > 0 && capacity >= n) {
+        const size_t bytes = sizeof(unsigned) * (size_t)n;
+        for (int k = 0; k < 2; k++) {
+            if (orders) HIP_TRY(c, hipMemcpy(orders + (size_t)k * n, c->blockOrder[k].p, bytes, hipMemcpyDeviceToHost));
+            if (costs) HIP_TRY(c, hipMemcpy(costs + (size_t)k * n, c->blockCost[k].p, bytes, hipMemcpyDeviceToHost));
+        }
+        if (ema) HIP_TRY(c, hipMemcpy(ema, c->blockEma.p, bytes, hipMemcpyDeviceToHost));
+    }
+    return n;
+}
+
+int rdh_debug_persist_set_order(rdh_ctx *c, const int32_t *order, int32_t n) {
+    if (!c) return RDH_ERR_ARGS;
+    if (!c->haveCamera) return fail(c, RDH_ERR_NO_SCENE, "no camera set (rdh_set_camera)");
+    const int blocks = makePixelMap(c).numBlocks;
+    if (!order || n != blocks) return fail(c, RDH_ERR_ARGS, "rdh_debug_persist_set_order: n = %d, the launch has %d blocks", n, blocks);
+    std::vector<char> seen((size_t)n, 0);
+    for (int k = 0; k < n; k++) {
+        if (order[k] < 0 || order[k] >= n || seen[(size_t)order[k]])
+            return fail(c, RDH_ERR_ARGS, "rdh_debug_persist_set_order: entry %d (%d) is out of range or listed twice", k, order[k]);
+        seen[(size_t)order[k]] = 1;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->testOrderBlocks = 0;  // (a HIP failure below leaves no half-written order pending)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // an earlier launch may still be reading the last one
+    if (int rc = grow(c, c->testOrder, (size_t)n, sizeof(int) * (size_t)n, Busy::Nothing)) return rc;
+    HIP_TRY(c, hipMemcpy(c->testOrder.p, order, sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    c->testOrderBlocks = n;
+    return RDH_OK;
 }
 
 int rdh_debug_wf_stamps(rdh_ctx *c, uint64_t *out, int64_t capacity, int32_t *stages, int32_t *waves) {
@@ -2922,7 +2988,7 @@ int treeHeaderPending(rdh_ctx *c, bool refit) {
     HIP_TRY(c, hipEventRecord(c->evTree, c->stream));
     c->scene.treePending = true;
     c->scene.treeRefit = refit;
-    c->orderValid = false;  // the persistent scheduler's block order belongs to the old geometry
+    restartSchedule(c);  // the persistent scheduler's block order belongs to the old geometry
     return RDH_OK;
 }
 
