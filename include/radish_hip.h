@@ -108,9 +108,9 @@ typedef struct rdh_counters {
 #define RDH_PT_RESTIR_FUSED 1024u /* rdh_restir_direct: round 1's pass 1, one lane per pixel with both walks inside the kernel
                                   (k_restir_pass1), instead of raygen / walk / RIS / walk / resolve (default; same results) */
 #define RDH_PT_WF_SMALL_LISTS 4096u /* for tests.  Wavefront: the per-stage lists of literal-class rays hold 4 entries, so that the
-                                  overflow path (such rays stay in the ordinary queues) runs.  rdh_gbuffer_render / rdh_restir_direct: a
-                                  wave walks its block as a packet for 4 visits only (256 normally), so that every block goes through
-                                  the hand-over to per-lane walks (traverse.h, packetWalk) */
+                                  overflow path (such rays stay in the ordinary queues) runs.  rdh_gbuffer_render / rdh_restir_direct /
+                                  stage 0 of the wavefront path: a wave walks its block as a packet for 4 visits only (256 normally), so
+                                  that every block goes through the hand-over to per-lane walks (traverse.h, packetWalk) */
 #define RDH_PT_PAIRS 32768u    /* per-lane walks over SIBLING PAIRS (one 64-byte record per inner node, shared by the six orderings: a lane
                                   that enters a node fetches both children and tests both boxes in one round trip; the far child is
                                   re-checked when the walk reaches it) instead of the six threaded arrays; same records, same counters.
@@ -120,10 +120,11 @@ typedef struct rdh_counters {
                                   rdh_trace_closest / rdh_trace_occluded (with RDH_PT_PERSISTENT) return RDH_ERR_UNSUPPORTED when
                                   the flag asks for pairs that do not exist */
 #define RDH_PT_NO_PAIRS 16384u /* never walk the sibling pairs */
-#define RDH_PT_NO_PACKETS 8192u /* rdh_gbuffer_render, rdh_restir_direct: primary rays lane by lane (the lane-refill walkers) instead of as
-                                  PACKETS — one 8x8 pixel block per wave, walked through the threaded order together with one uniform
-                                  node load per visit (traverse.h, packetWalk); same records, same counters.  (rdh_path_trace keeps its
-                                  primary rays in trace(0): measured) */
+#define RDH_PT_NO_PACKETS 8192u /* rdh_gbuffer_render, rdh_restir_direct, and stage 0 of the wavefront path tracer (rdh_path_trace*
+                                  with RDH_PT_WAVEFRONT): primary rays lane by lane (the lane-refill walkers; wavefront: k_wf_trace at
+                                  k = 0) instead of as PACKETS — one 8x8 pixel block per wave, walked through the threaded order
+                                  together with one uniform node load per visit (traverse.h, packetWalk; wavefront:
+                                  k_wf_trace_primary); same records, same counters */
 #define RDH_PT_AUTO 65536u     /* rdh_path_trace / rdh_path_trace_gathered*: the library picks the structure by what this launch holds —
                                   the wavefront pipeline with material sort and three sub-frames for a big tree (>= 100 000 nodes) and a
                                   big share of the frame (>= 12 000 8x8 blocks: a 1080p frame, or half of one), else the persistent kernel

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(64, COUNT ? 1 : 7) void k_walk_pair(DScene s, const
 // instead of one L1 request per lane.  Same records, same counters as the lane-refill walkers; on rays that do not travel together
 // it is merely slow (a wave then visits the union of 64 unrelated walks), so the caller says when a list is coherent.
 // Literal-class rays: set aside for the workgroup-per-item launch when they were listed (deferAll), else traced whole by the wave,
-// in place, one after the other.
+// in place, one after the other.  (deferAll is the lane's own: k_wf_trace_primary, kernels_wave.h, passes "this slot is listed".)
 template <bool COUNT, bool DEFER, class Work>
 RD_DEV void walkPacket(const DScene &s, long long chunk, bool deferAll, int budget, Work &work) {
     const int lane = int(threadIdx.x) & 63;

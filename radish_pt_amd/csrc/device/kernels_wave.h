@@ -12,7 +12,8 @@
 // Launch structure per frame (maxDepth = D):  memset(counters) · raygen · for k = 0..D { trace(k) · shade(k) } · finish
 // (optionally as three sub-frames on three streams, see k_wf_raygen; the material sort happens inside shade, see k_wf_shade)
 //   trace(k)  = closest-hit for the rays of bounce k, then any-hit for the shadow rays emitted by shade(k-1): one queue of work
-//               items, the (long) extension rays handed out first so that the stage ends on the (short) shadow rays
+//               items, the (long) extension rays handed out first so that the stage ends on the (short) shadow rays.  trace(0) has
+//               primary rays only, an 8x8 block per 64 items: k_wf_trace_primary walks them as packets in place of k_wf_trace
 //   shade(k)  = surface fetch for hit k, emitter/miss termination, then bounce body k+1 (NEE sample → shadow
 //               queue, BSDF sample → next ray queue) with wave64 ballot compaction
 // trace and shade are persistent kernels: a fixed grid of waves pulls 64-item packets from device-side queue
@@ -21,6 +22,7 @@
 #include "kernels_pt.h"
 #include "wg_trace.h"
 #include "ray_cull.h"
+#include "kernels_walk.h"
 
 namespace rd {
 
@@ -651,6 +653,74 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PAIRS && !C
     }
     RD_WF_STAMP(2);
     if (COUNT) flushCounters(s.counters, nClosest, nAny, nHits, ws);
+}
+
+// ---- trace(0) as PACKETS ---------------------------------------------------------------------------------------------------------
+// Stage 0 is the one trace stage whose rays travel together: its queue is the identity, so the 64 items of 64-slot group g are the
+// primary rays of one 8x8 block (k_wf_raygen; k_ad_raygen: one block's pixels, a pixel's samples side by side).  k_wf_trace walks
+// them like any stage's, a record fetch per lane and visit, at the walkers' request-rate ceiling; the packet walk
+// (traverse.h, packetWalk; kernels_walk.h, walkPacket) makes the same visits with one scalar record load per visit for the wave.
+// So this kernel is launched INSTEAD of k_wf_trace<..>(k = 0) (radish_hip.hip, wavefrontStages; RDH_PT_NO_PACKETS keeps that one):
+// one wave per group, four groups per workgroup, no ticket, no head, no pull — the host knows rayCount[0] = 64 nGroups.  A kernel
+// of its own: k_wf_trace's pair variant sits on its register step.
+//
+// A slot of stage 0 as walkPacket's work: the item is the queue entry, the record is the hit record k_wf_trace's retire step writes.
+struct WfSlotWork {
+    const WaveWorkspace &w;
+    int p;  // the path slot taken last
+
+    RD_DEV bool find(long long chunk, int slot) {
+        const int e = w.rayq[0][chunk * 64 + slot];
+        p = e <= -2 ? -2 - e : e;  // -2 - slot: on the first list as well (k_wf_raygen)
+        return e != -1;            // -1: a pixel outside the frame
+    }
+    RD_DEV Ray ray(float &tmax) const { return wfSlotRay(w, 0, p, false, tmax); }
+    RD_DEV void store(const DScene &s, const RaySlab &, int hitPrim, v2 hitBary, float, bool) const {
+        const bool hit = hitPrim != -1;
+        w.hit[p] = make_int4(hitPrim, __float_as_int(hit ? hitBary.x : 0.f), __float_as_int(hit ? hitBary.y : 0.f),
+                             hit ? int(s.primClass[hitPrim]) : 0);
+    }
+};
+// The first list, in the same launch: workgroup b < min(nLit, G) traces the entries b, b + G, ... together (wgTraceWhole) before its
+// waves take their groups, so the handful of literal-class primary rays (several hundred microseconds each for a workgroup) start
+// with the launch and the other workgroups' packets run beside them, as k_wf_trace hides its list behind its ordinary rays.
+// Who traces a listed ray is decided by the ray both sides build (wfSlotRay, makeRaySlab): the list if raySetAside(class) — the
+// classes that wander, 1..4 — else the lane that owns the slot, in its packet (class 0: the hint did not hold) or whole (class 5).
+// An entry beyond the list's capacity stayed in the queue as a plain slot, and its own wave traces it whole, in place.
+#ifndef RD_WF_PRIMARY_WAVES
+#define RD_WF_PRIMARY_WAVES 1  // waves per SIMD the kernel is held to (1: whatever its registers allow)
+#endif
+template <bool COUNT>
+__global__ __launch_bounds__(256, COUNT ? 1 : RD_WF_PRIMARY_WAVES) void k_wf_trace_primary(DScene s, WaveWorkspace w, int nGroups, int budget) {
+    __shared__ WgTraceSharedT<256> wgsh;
+    const int nLit = w.ctr->litCount[0].v < w.litCap ? w.ctr->litCount[0].v : w.litCap;
+    WalkStats ws{0, 0};
+    unsigned nClosest = 0, nHits = 0;
+    for (int it = int(blockIdx.x); it < nLit; it += int(gridDim.x)) {  // uniform over the workgroup
+        const int pp = w.litq[0][it];  // (stage 0 lists extension rays only)
+        float lim;
+        const Ray ray = wfSlotRay(w, 0, pp, false, lim);
+        const RaySlab urs = makeRaySlab(ray);
+        if (!raySetAside(urs.cls) || s.bvhSize == 0) continue;  // walkPacket's condition: the slot's own lane has this one
+        const CoopTrace ct = wgTraceWhole<false, 256>(s, s.nodes[getMTBVHId(-ray.d)], urs, lim, wgsh);
+        if (threadIdx.x == 0) {  // the record of the finished ray (as in k_wf_trace)
+            nClosest++;
+            const bool hit = ct.hitPrim != -1;
+            if (hit) nHits++;
+            w.hit[pp] = make_int4(ct.hitPrim, __float_as_int(hit ? ct.bary.x : 0.f), __float_as_int(hit ? ct.bary.y : 0.f),
+                                  hit ? int(s.primClass[ct.hitPrim]) : 0);
+            if (COUNT) {
+                ws.nodes += ct.nodes;
+                ws.tris += ct.tris;
+            }
+        }
+    }
+    if (COUNT && threadIdx.x < 64u) flushCounters(s.counters, nClosest, 0u, nHits, ws);  // (wave 0: lane 0 holds the list's counts)
+    const int group = int(blockIdx.x) * 4 + int(threadIdx.x >> 6);
+    if (group >= nGroups) return;
+    const bool listed = w.rayq[0][(size_t)group * 64 + (threadIdx.x & 63u)] <= -2;  // this lane's ray is the list's if it is set aside
+    WfSlotWork work{w, -1};
+    walkPacket<COUNT, true>(s, group, listed, budget, work);
 }
 
 // ---- shade(k): hit k → terminate or run bounce body k+1 ----------------------------------------------------------

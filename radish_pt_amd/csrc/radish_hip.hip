@@ -694,6 +694,7 @@ bool usePackets(uint32_t flags) {
     static const int env = getenv("RADISH_PACKETS") ? atoi(getenv("RADISH_PACKETS")) : 1;
     return env != 0 && !(flags & RDH_PT_NO_PACKETS);
 }
+int packetBudget(uint32_t flags) { return (flags & RDH_PT_WF_SMALL_LISTS) ? 4 : kPacketBudget; }  // tests: packets of 4 visits
 
 // Grid for "4 waves per workgroup, one 8x8 block per wave", padded to a multiple of 8 workgroups (xcdSwizzle).
 unsigned gridFor(const PixelMap &pm) {
@@ -844,6 +845,10 @@ struct WfLaunch {
     bool count, sort, walkAll, tree;
     unsigned traceGrid, shadeGrid;
     int parts;  // pipelines: what the caller asked for, or 1 where the pair walkers' strips would exceed their budget
+    // stage 0 as packets (kernels_wave.h, k_wf_trace_primary): the 64-slot groups of each pipeline's stage 0, rayCount[0] / 64, which
+    // the caller fills in for the raygen it launches; 0: k_wf_trace runs stage 0 as it runs every other one
+    unsigned primaryGroups[kWfParts] = {0, 0, 0};
+    int primaryBudget = 0;
 };
 int wavefrontPrepare(rdh_ctx *c, int maxDepth, uint32_t flags, int parts, WfLaunch &L) {
     if (maxDepth > kMaxWaveDepth) return fail(c, RDH_ERR_ARGS, "maxDepth %d exceeds %d", maxDepth, kMaxWaveDepth);
@@ -915,6 +920,8 @@ int wavefrontPrepare(rdh_ctx *c, int maxDepth, uint32_t flags, int parts, WfLaun
         if (flags & RDH_PT_WF_SMALL_LISTS) c->wf[h].litCap = 4;  // tests: what does not fit stays in the ordinary queues
     }
     L = WfLaunch{count, sort, walkAll, tree, traceGrid, shadeGrid, parts};
+    // stage 0's primary rays as packets, unless told otherwise (the A/B switch within one build); an empty tree keeps k_wf_trace
+    L.primaryBudget = (usePackets(flags) && c->scene.ds.bvhSize > 0) ? packetBudget(flags) : 0;
     return RDH_OK;
 }
 
@@ -931,9 +938,16 @@ void wavefrontStages(rdh_ctx *c, const WfLaunch &L, int maxDepth, uint32_t flags
             hipStream_t st = sts[h];
             WaveWorkspace &w = c->wf[h];
             long pe = (h == 0 && L.parts == 1) ? profBegin(c, flags) : -1;
-            withBools([&](auto cnt, auto pr) {
-                hipLaunchKernelGGL((k_wf_trace<cnt.value, pr.value>), dim3(L.traceGrid), dim3(256), 0, st, c->scene.ds, w, k);
-            }, L.count, L.tree);
+            if (k == 0 && L.primaryBudget > 0 && L.primaryGroups[h] > 0) {  // one wave per 64-slot group, walked as a packet
+                withBools([&](auto cnt) {
+                    hipLaunchKernelGGL((k_wf_trace_primary<cnt.value>), dim3((L.primaryGroups[h] + 3u) / 4u), dim3(256), 0, st, c->scene.ds, w,
+                                       (int)L.primaryGroups[h], L.primaryBudget);
+                }, L.count);
+            } else {
+                withBools([&](auto cnt, auto pr) {
+                    hipLaunchKernelGGL((k_wf_trace<cnt.value, pr.value>), dim3(L.traceGrid), dim3(256), 0, st, c->scene.ds, w, k);
+                }, L.count, L.tree);
+            }
             profEnd(c, pe);
             hipLaunchKernelGGL(k_wf_shade, dim3(L.shadeGrid), dim3(256), 0, st, c->scene.ds, w, k, maxDepth, L.sort ? 1 : 0,
                                (const float4 *)c->scene.emitBox, L.walkAll ? 1 : 0);
@@ -974,6 +988,7 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
         WaveWorkspace &w = c->wf[h];
         const unsigned nLocal = (unsigned)(pm.numBlocks - h + parts - 1) / (unsigned)parts;
         const unsigned gridBlk = (((nLocal * (unsigned)samples + 3u) / 4u + 7u) / 8u) * 8u;
+        L.primaryGroups[h] = nLocal * (unsigned)samples;  // k_wf_raygen's nGroups
         keep(hipMemsetAsync(w.ctr, 0, sizeof(WaveCounters), st), "hipMemsetAsync(wavefront counters)");
         hipLaunchKernelGGL(k_wf_raygen, dim3(gridBlk), dim3(256), 0, st, c->scene.ds, c->cam, pm, w, looper, samples, h, parts);
     }
@@ -1014,8 +1029,6 @@ uint32_t resolveStructure(const rdh_ctx *c, const PixelMap &pm, uint32_t flags) 
     const bool wavefront = c->scene.ds.bvhSize >= 100000 && pm.numBlocks >= 12000;
     return flags | (wavefront ? (RDH_PT_WAVEFRONT | RDH_PT_SORT_MATERIAL | RDH_PT_WF_SUBFRAMES) : RDH_PT_PERSISTENT);
 }
-
-int packetBudget(uint32_t flags) { return (flags & RDH_PT_WF_SMALL_LISTS) ? 4 : kPacketBudget; }  // tests: packets of 4 visits
 
 // k_walk_persistent over a ray list (d_hits xor d_occ): as many single-wave workgroups as stay resident, lane refill.
 // deferCount / deferList (ReSTIR's lists): literal-class rays have been listed by the producer of `d_rays`; they are traced one
@@ -1622,6 +1635,7 @@ int rdh_path_trace_adaptive(rdh_ctx *c, float *d_direct, float *d_indirect, int3
     hipLaunchKernelGGL(k_ad_raygen, dim3(genGrid), dim3(256), 0, c->stream, c->scene.ds, c->cam, pm, w, looper, (const int *)d_count,
                        (const int *)owner, (int)T);
     keepHip(c, rc, hipGetLastError(), "k_ad_raygen");
+    L.primaryGroups[0] = (unsigned)(padded / 64);  // k_ad_raygen's nGroups
     wavefrontStages(c, L, maxDepth, flags, rc);
     if (rc == RDH_OK) {
         hipLaunchKernelGGL(k_ad_finish, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, pm, w, (const int *)owner, (int)T,
