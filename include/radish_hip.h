@@ -361,6 +361,42 @@ int rdh_build_light_list_device(rdh_ctx *ctx, const float *d_vertices, const int
 int rdh_scene_set_texture(rdh_ctx *ctx, int32_t texId, const float *d_texels, int32_t width, int32_t height);
 int rdh_scene_env_power(rdh_ctx *ctx, float *out);
 long long rdh_debug_read_textures(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
+/* ---- the lens: depth of field ------------------------------------------------------------------------------------------------
+ * The reference's Camera::sample leaves the aperture point at 0 (a pinhole, whatever lensRadius is); rdh_set_lens says how the
+ * primary ray's third and fourth draw, which every path draws and the pinhole discards, pick a point pAperture on the unit aperture.
+ * pLens = pAperture * lensRadius; the ray leaves position + right * pLens.x + up * pLens.y towards the pixel's point on the focal
+ * plane, (ruv * (aspect, 1) * tanFovY, 1) * focalDist, as Camera::sample is written.  The draw cursor behind the primary ray is 4
+ * in every mode.
+ *   RDH_LENS_OFF   pAperture = 0: the reference's frames, bit for bit (the default, and the state after every rdh_scene_upload /
+ *                  rdh_scene_free).
+ *   RDH_LENS_DISK  pAperture = concentricSampleDisk(r.z, r.w), a round aperture.
+ *   RDH_LENS_MASK  texture maskTexId of the uploaded scene (w x h texels, n = w * h) is the aperture over [-1, 1]^2: texel k is
+ *                  chosen with probability luminance(texel k) / sum by an alias table over the n luminances in texel order
+ *                  (k0 = min(int(float(n) * r.z), n - 1); k = r.w < prob[k0] ? k0 : failId[k0]), and the point inside it from
+ *                  what the lookup leaves of the draws: jx = float(n) * r.z - float(k0), jy = r.w / prob or (r.w - prob) /
+ *                  (1 - prob), each clamped to [0, 1); u = (col + jx) / w, v = (row + jy) / h, pAperture = (1 - 2u, 1 - 2v): the
+ *                  flip the screen coordinate gets, so the mask lies on the aperture as it would on the screen.
+ * While the mode is not OFF and the camera's lensRadius > 0, rdh_path_trace, _samples, _adaptive, _direct, _gathered(_all) and
+ * rdh_dump_rays trace lens rays in every structure (a pixel's ray depends on its own index and Sobol row only, so tile partitions
+ * agree with whole frames); with lensRadius <= 0 they launch the pinhole kernels.  The G-buffer and the denoisers stay the
+ * pinhole's (renderGBuffer hard-codes pLens = 0), and rdh_restir_direct* return RDH_ERR_UNSUPPORTED with nothing enqueued.
+ * rdh_set_lens: DISK and MASK need an uploaded scene (RDH_ERR_NO_SCENE).  MASK derives the luminances and the table on the device,
+ * into storage that lives and dies with the scene (28 B per texel), with rdh_build_alias_table_device's kernels: a one-off cost that
+ * grows linearly with n, and one host wait for the luminances' sum.  An unknown mode, a maskTexId outside
+ * [0, numTextures), or a mask whose luminances sum to 0 or to something not finite: RDH_ERR_ARGS, and the previous mode and table
+ * stay in force (a bad mode or id enqueues nothing; a bad sum is known once the weight kernels have run).  rdh_scene_set_texture on
+ * the mask's texture while MASK is set derives the table again in the same call, from the new texels, and refuses a mask without an
+ * aperture (RDH_ERR_ARGS, the scene unchanged); this costs that call the same host wait.
+ * rdh_debug_primary_rays: test access: d_rays6 float[H][W][6] (DEVICE) <- {origin, direction} of every pixel's primary ray at Sobol
+ * row `looper`, from the draw and the cameraSample call the tracers make (this rank's pixels on a tile partition).  Asynchronous.
+ * rdh_debug_read_lens: test access: which = 0 {int32 mode, maskTexId (-1 unless MASK), w, h} (16 B), 1 the mask's alias table
+ * (w x h x 8 B; nothing unless MASK).  Returns the byte size (hostOut NULL: only that) or a negative RDH_ERR_*.  Blocking. */
+#define RDH_LENS_OFF 0
+#define RDH_LENS_DISK 1
+#define RDH_LENS_MASK 2
+int rdh_set_lens(rdh_ctx *ctx, int mode, int32_t maskTexId);
+int rdh_debug_primary_rays(rdh_ctx *ctx, int looper, float *d_rays6);
+long long rdh_debug_read_lens(rdh_ctx *ctx, int which, void *hostOut, long long maxBytes);
 /* ---- the triangle set replaced on the device -----------------------------------------------------------------------------
  * rdh_scene_set_geometry: the uploaded scene's triangles are replaced by numPrims triangles from DEVICE arrays, all four required
  * (the count may differ from the current one): d_vertices and d_normals float[3*numPrims][3], d_texcoords float[3*numPrims][2],

@@ -47,6 +47,9 @@ RDH_PT_WALK_ALL = 131072
 # BVH builders of rdh_build_bvh_device_ex / rdh_scene_update_geometry_ex (Context.build_bvh_device / update_geometry `builder`)
 RDH_BVH_SAH, RDH_BVH_LBVH = 0, 1
 BVH_BUILDERS = {"sah": RDH_BVH_SAH, "lbvh": RDH_BVH_LBVH}
+# rdh_set_lens (Context.set_lens `mode`)
+RDH_LENS_OFF, RDH_LENS_DISK, RDH_LENS_MASK = 0, 1, 2
+LENS_MODES = {"off": RDH_LENS_OFF, "disk": RDH_LENS_DISK, "mask": RDH_LENS_MASK}
 # rdh_scene_pose_objects: what happens to the tree (Context.pose_objects `tree`) and its flag
 RDH_POSE_REFIT, RDH_POSE_SAH, RDH_POSE_LBVH = 0, 1, 2
 RDH_POSE_REBUILD_LIGHTS = 1
@@ -79,6 +82,7 @@ EXPORTS = [
     "rdh_scene_set_geometry", "rdh_debug_read_geometry",
     "rdh_path_trace_adaptive", "rdh_adaptive_plan",
     "rdh_debug_persist_schedule", "rdh_debug_persist_read", "rdh_debug_persist_set_order",
+    "rdh_set_lens", "rdh_debug_primary_rays", "rdh_debug_read_lens",
 ]
 
 
@@ -252,6 +256,17 @@ def persist_entries():
     read.argtypes, read.restype = [vp, vp, vp, vp, vp, i32], i32
     set_order.argtypes, set_order.restype = [vp, vp, i32], i32
     return sched, read, set_order
+
+
+def lens_entries():
+    """(rdh_set_lens, rdh_debug_primary_rays, rdh_debug_read_lens) with their signatures; bound at first use for the same reason
+    as adaptive_entries."""
+    vp, i32 = C.c_void_p, C.c_int32
+    set_lens, rays, read = lib().rdh_set_lens, lib().rdh_debug_primary_rays, lib().rdh_debug_read_lens
+    set_lens.argtypes, set_lens.restype = [vp, i32, i32], i32
+    rays.argtypes, rays.restype = [vp, i32, vp], i32
+    read.argtypes, read.restype = [vp, i32, vp, C.c_int64], C.c_int64
+    return set_lens, rays, read
 
 
 class RadishError(RuntimeError):
@@ -555,6 +570,50 @@ class Context:
         if which == 0:
             return out.view(np.float32)
         return out.view(L.BINOMIAL_DTYPE) if which == 1 else out
+
+    # ---- the lens: depth of field ----
+    def set_lens(self, mode, mask_tex_id=-1):
+        """How primary rays pick their point on the lens (rdh_set_lens): "off" (the pinhole, the default and the state after
+        every upload_scene), "disk" (a round aperture) or "mask" (texture mask_tex_id of the uploaded scene is the aperture's
+        shape, e.g. SceneData.aperture_mask_tex_id; its alias table is built on the device in this call, which waits for it
+        once).  The camera's lens_radius and focal_dist (hostlib.make_camera) are the aperture's size and the focal plane; with
+        lens_radius 0 frames are the pinhole's.  path_trace, path_trace_samples, path_trace_adaptive, path_trace_direct and
+        dump_rays follow the lens; the G-buffer and the denoisers do not, and restir_direct raises while a lens is active.  A
+        scene file's LensRadius / ApertureMask switch nothing on: the caller does.  The reference-style shim (Camera / pathTrace)
+        has no counterpart: the reference leaves its lens dead."""
+        if mode not in LENS_MODES:
+            raise RadishError(f"set_lens: mode must be one of {sorted(LENS_MODES)}, got {mode!r}")
+        self.check(lens_entries()[0](self.h, LENS_MODES[mode], int(mask_tex_id)))
+
+    def debug_primary_rays(self, looper):
+        """Test access (rdh_debug_primary_rays): every pixel's primary ray at Sobol row `looper`, a float32 cuda tensor
+        [height, width, 6] = {origin, direction}, from the draw and the camera function the tracers use."""
+        torch = _torch()
+        if getattr(self, "width", None) is None:
+            raise RadishError("debug_primary_rays: no camera set")
+        w, h = self.width, self.height
+        rays = torch.zeros(h, w, 6, dtype=torch.float32, device=f"cuda:{self.device}")
+        self.check(lens_entries()[1](self.h, int(looper), rays.data_ptr()))
+        return rays
+
+    def debug_read_lens(self):
+        """Blocking test access (rdh_debug_read_lens): (mode name, mask texture id, width, height, the mask's alias table as
+        layouts.BINOMIAL_DTYPE — empty unless the mode is "mask")."""
+        read = lens_entries()[2]
+        head = np.zeros(4, np.int32)
+        rc = read(self.h, 0, head.ctypes.data, 16)
+        if rc < 0:
+            self.check(int(rc))
+        n = read(self.h, 1, None, 0)
+        if n < 0:
+            self.check(int(n))
+        table = np.zeros(n, np.uint8)
+        if n:
+            rc = read(self.h, 1, table.ctypes.data, n)
+            if rc < 0:
+                self.check(int(rc))
+        names = {v: k for k, v in LENS_MODES.items()}
+        return names[int(head[0])], int(head[1]), int(head[2]), int(head[3]), table.view(L.BINOMIAL_DTYPE)
 
     # ---- the triangle set replaced on the device (DESIGN 11i) ----
     def set_geometry(self, vertices, normals, texcoords, material_ids, builder="sah", env_power=0.0):

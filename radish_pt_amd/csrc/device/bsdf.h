@@ -40,14 +40,26 @@ RD_DEV v4 sample4D(Sampler &s) {
     return {a, b, c, d};
 }
 
+// ---- the lens (no reference counterpart: Camera::sample leaves pAperture at 0) ----
+// The mode is wave-uniform (a kernel argument); `alias` is the alias table over the mask's w * h texel luminances, in texel order.
+enum LensMode { LensOff = 0, LensDisk = 1, LensMask = 2 };  // RDH_LENS_*
+struct DLens {
+    const AliasRec *alias;
+    int mode, w, h;
+};
+RD_DEV v2 lensAperture(const DLens &lens, float rz, float rw);  // below, behind concentricSampleDisk
+
 // ---- Camera::sample (sceneStructs.h:72-91) ----
-RD_DEV Ray cameraSample(const DCamera &c, int x, int y, v4 r) {
+// LENS is chosen by the host: the <false> instantiations are the reference's pinhole and never look at `lens`.
+template <bool LENS = false>
+RD_DEV Ray cameraSample(const DCamera &c, int x, int y, v4 r, const DLens &lens = DLens{}) {
     float aspect = float(c.resx) / float(c.resy);
     v2 pixelSize = {1.f / float(c.resx), 1.f / float(c.resy)};
     v2 scr = mk2(float(x), float(y)) * pixelSize;
     v2 ruv = scr + pixelSize * mk2(r.x, r.y);
     ruv = {1.f - ruv.x * 2.f, 1.f - ruv.y * 2.f};
     v2 pAperture = {0.f, 0.f};
+    if (LENS) pAperture = lensAperture(lens, r.z, r.w);
     v3 pLens = {pAperture.x * c.lensRadius, pAperture.y * c.lensRadius, 0.f};
     v2 f = (ruv * mk2(aspect, 1.f)) * c.tanFovY;
     v3 pFocus = mk3(f.x, f.y, 1.f) * c.focalDist;
@@ -91,6 +103,29 @@ RD_DEV v2 concentricSampleDisk(float x, float y) {  // :132-136
     float s, c;
     sincos_det(theta, s, c);
     return {r * c, r * s};
+}
+// The point on the unit aperture that the primary ray's two lens draws select.  DISK: the concentric disk.  MASK: texel k of the
+// mask by its luminance (the alias lookup of lightAliasSample), then a point inside the texel from what the lookup left of the
+// two draws — rz's fraction beyond its entry, and rw rescaled to [0, 1) on whichever side of `prob` it fell — flipped as ruv is,
+// so that the mask lies on the aperture as it lies on the screen.
+RD_DEV v2 lensAperture(const DLens &lens, float rz, float rw) {
+    if (lens.mode == LensDisk) return concentricSampleDisk(rz, rw);
+    const float oneBelow = 0x1.fffffep-1f;
+    const int n = lens.w * lens.h;
+    const float fn = float(n) * rz;
+    const int k0 = imin(int(fn), n - 1);
+    const AliasRec rec = lens.alias[k0];
+    const bool take = rw < rec.prob;
+    const int k = take ? k0 : rec.failId;
+    float jx = fn - float(k0);
+    float jy = take ? rw / rec.prob : (rw - rec.prob) / (1.f - rec.prob);
+    jx = jx < 0.f ? 0.f : jx;
+    jx = jx > oneBelow ? oneBelow : jx;
+    jy = jy < 0.f ? 0.f : jy;
+    jy = jy > oneBelow ? oneBelow : jy;
+    const int row = k / lens.w, col = k - row * lens.w;
+    const float u = (float(col) + jx) / float(lens.w), v = (float(row) + jy) / float(lens.h);
+    return {1.f - 2.f * u, 1.f - 2.f * v};
 }
 RD_DEV m3 localRefMatrix(v3 n) {  // :149-155
     v3 t = (fabs_(n.y) > 0.9999f) ? mk3(0.f, 0.f, 1.f) : mk3(0.f, 1.f, 0.f);

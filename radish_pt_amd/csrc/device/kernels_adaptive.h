@@ -102,8 +102,9 @@ __global__ __launch_bounds__(256) void k_ad_scatter(PixelMap pm, const int *__re
 // One lane per slot of the total padded to 64.  What it writes for a slot is what k_wf_raygen writes for the slot of that pixel and
 // row: set 0 of the riding state, both accumulators zero, literal-class primary rays on stage 0's first list; the padding of the
 // last 64-group gets -1 in rayq[0], and rayCount[0] is the padded total.
-__global__ __launch_bounds__(256) void k_ad_raygen(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper,
-                                                   const int *__restrict__ count, const int *__restrict__ owner, int total) {
+template <bool LENS>  // written once for k_ad_raygen and k_ad_raygen_lens, as wfRaygen (kernels_wave.h)
+RD_DEV void adRaygen(const DScene &s, const DCamera &cam, const PixelMap &pm, const WaveWorkspace &w, int looper,
+                     const int *__restrict__ count, const int *__restrict__ owner, int total, const DLens &lens) {
     unsigned wg;
     const unsigned nGroups = ((unsigned)total + 63u) >> 6;
     const bool wgValid = xcdSwizzle(blockIdx.x, (nGroups + 3u) >> 2, wg);
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void k_ad_raygen(DScene s, DCamera cam, PixelM
         // the pixel's own row: count < 2^31, looper < 10000, j < 16, so the unsigned sum is exact
         const unsigned row = ((unsigned)looper + (unsigned)count[px.out] + j) % (unsigned)kSobolRows;
         Sampler rng = makeSeededRandomEngine(int(row), px.index, 0, s.sobol);
-        Ray ray = cameraSample(cam, px.x, px.y, sample4D(rng));
+        Ray ray = cameraSample<LENS>(cam, px.x, px.y, sample4D(rng), lens);
         w.ro[0][p] = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.f);
         w.rd[0][p] = make_float4(ray.d.x, ray.d.y, ray.d.z, 0.f);
         w.accD[p] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -136,6 +137,15 @@ __global__ __launch_bounds__(256) void k_ad_raygen(DScene s, DCamera cam, PixelM
     }
     if (inRange) w.rayq[0][p] = valid ? (listed ? -2 - p : p) : -1;
     if (blockIdx.x == 0 && threadIdx.x == 0) w.ctr->rayCount[0].v = int(nGroups) * 64;
+}
+__global__ __launch_bounds__(256) void k_ad_raygen(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper,
+                                                   const int *__restrict__ count, const int *__restrict__ owner, int total) {
+    adRaygen<false>(s, cam, pm, w, looper, count, owner, total, DLens{});
+}
+__global__ __launch_bounds__(256) void k_ad_raygen_lens(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper,
+                                                        const int *__restrict__ count, const int *__restrict__ owner, int total,
+                                                        DLens lens) {
+    adRaygen<true>(s, cam, pm, w, looper, count, owner, total, lens);
 }
 
 // ---- finish -------------------------------------------------------------------------------------------------------------------

@@ -180,12 +180,12 @@ __global__ __launch_bounds__(kScheduleThreads) void k_persist_schedule(unsigned 
 #ifndef RD_PERSIST_PAIR_WAVES
 #define RD_PERSIST_PAIR_WAVES 3  // the pair variant is held to three waves per SIMD (173 VGPRs otherwise: two)
 #endif
-template <bool COUNT, bool PAIRS = false>
+template <bool COUNT, bool PAIRS = false, bool LENS = false>
 __global__ __launch_bounds__(64, PAIRS && !COUNT ? RD_PERSIST_PAIR_WAVES : RD_PERSIST_WAVES) void k_pt_persistent(DScene s, DCamera cam, PixelMap pm, int looper, int iter, int maxDepth,
                                                        float *__restrict__ directIllum, float *__restrict__ indirectIllum,
                                                        PersistCounters *pc, const int *__restrict__ blockOrder,
                                                        unsigned *__restrict__ blockCost, int2 *__restrict__ pairOvf = nullptr,
-                                                       int pairOvfDepth = 0) {
+                                                       int pairOvfDepth = 0, DLens lens = DLens{}) {
     // ---- LDS-resident path state (SoA: lane-consecutive, conflict-free) ----
     // One wave per workgroup: nothing here needs a workgroup barrier, and a finished wave frees its CU slot at once
     // (with 4-wave workgroups the slot stays taken until the slowest of the four has drained its last path).
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(64, PAIRS && !COUNT ? RD_PERSIST_PAIR_WAVES : RD_PE
                         myBlock = int(blk);
                         pathSteps = 0;
                         Sampler rng = makeSeededRandomEngine(looper, px.index, 0, s.sobol);
-                        Ray ray = cameraSample(cam, px.x, px.y, sample4D(rng));
+                        Ray ray = cameraSample<LENS>(cam, px.x, px.y, sample4D(rng), lens);
                         rngScramble = rng.scramble;
                         rngPtr = rng.ptr;
                         sAccD[0][t] = sAccD[1][t] = sAccD[2][t] = 0.f;

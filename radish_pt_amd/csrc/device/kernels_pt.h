@@ -127,10 +127,13 @@ RD_DEV void dumpRay(const RayDump &d, int which, v3 a, v3 b) {
 }
 
 // ---- singleKernelPT (pathtrace.cu:149-291) ----------------------------------------------------------------
-template <bool COUNT, bool DUMP = false>
+// LENS (here and in every kernel that makes primary rays): the host picks the instantiation, <.., false> while the lens is off
+// or its radius 0, so the pinhole kernels are the code they were; `lens` is read by the <.., true> ones only.
+template <bool COUNT, bool DUMP = false, bool LENS = false>
 __global__ __launch_bounds__(256) void k_path_trace_mega(DScene s, DCamera cam, PixelMap pm, int looper, int iter,
                                                          int maxDepth, float *__restrict__ directIllum,
-                                                         float *__restrict__ indirectIllum, RayDump dump = RayDump{}) {
+                                                         float *__restrict__ indirectIllum, RayDump dump = RayDump{},
+                                                         DLens lens = DLens{}) {
     Pix px = mapWavePixel(pm);  // single-wave workgroups: 64 threads, one 8x8 block each
     WalkStats ws{0, 0};
     unsigned nClosest = 0, nAny = 0, nHits = 0;
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(256) void k_path_trace_mega(DScene s, DCamera cam, 
     if (px.valid) {
         v3 direct = mk3(0.f), indirect = mk3(0.f);
         Sampler rng = makeSeededRandomEngine(looper, px.index, 0, s.sobol);
-        Ray ray = cameraSample(cam, px.x, px.y, sample4D(rng));
+        Ray ray = cameraSample<LENS>(cam, px.x, px.y, sample4D(rng), lens);
         if (DUMP) dumpRay(dump, 0, ray.o, ray.d);
         HitRec h = traceClosest<COUNT>(s, ray, ws);
         nClosest++;
@@ -218,16 +221,16 @@ __global__ __launch_bounds__(256) void k_path_trace_mega(DScene s, DCamera cam, 
 }
 
 // ---- PTDirectKernel (pathtrace.cu:293-345) ------------------------------------------------------------------
-template <bool COUNT>
+template <bool COUNT, bool LENS = false>
 __global__ __launch_bounds__(256) void k_path_trace_direct(DScene s, DCamera cam, PixelMap pm, int looper, int iter,
-                                                           float *__restrict__ directIllum) {
+                                                           float *__restrict__ directIllum, DLens lens = DLens{}) {
     Pix px = mapWavePixel(pm);  // single-wave workgroups: 64 threads, one 8x8 block each
     WalkStats ws{0, 0};
     unsigned nClosest = 0, nAny = 0, nHits = 0;
     if (px.valid) {
         v3 direct = mk3(0.f);
         Sampler rng = makeSeededRandomEngine(looper, px.index, 0, s.sobol);
-        Ray ray = cameraSample(cam, px.x, px.y, sample4D(rng));
+        Ray ray = cameraSample<LENS>(cam, px.x, px.y, sample4D(rng), lens);
         HitRec h = traceClosest<COUNT>(s, ray, ws);
         nClosest++;
         do {
@@ -263,6 +266,20 @@ __global__ __launch_bounds__(256) void k_path_trace_direct(DScene s, DCamera cam
         storeRunningMean(directIllum, px.out, direct, iter);
     }
     if (COUNT) flushCounters(s.counters, nClosest, nAny, nHits, ws);
+}
+
+// ---- the primary rays alone (rdh_debug_primary_rays: tests) -----------------------------------------------------------------
+// Every pixel's {origin, direction} in frame layout, from the draw and the cameraSample call of the tracers above.
+template <bool LENS>
+__global__ __launch_bounds__(256) void k_primary_rays(DScene s, DCamera cam, PixelMap pm, int looper, float *__restrict__ rays6,
+                                                      DLens lens) {
+    Pix px = mapWavePixel(pm);
+    if (!px.valid) return;
+    Sampler rng = makeSeededRandomEngine(looper, px.index, 0, s.sobol);
+    Ray ray = cameraSample<LENS>(cam, px.x, px.y, sample4D(rng), lens);
+    float *o = rays6 + 6ll * px.index;
+    o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z;
+    o[3] = ray.d.x; o[4] = ray.d.y; o[5] = ray.d.z;
 }
 
 // ---- renderGBuffer (gBuffer.cu:3-76) --------------------------------------------------------------------------

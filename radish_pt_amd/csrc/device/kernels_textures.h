@@ -26,6 +26,13 @@ __global__ __launch_bounds__(256) void k_env_weights(const float *__restrict__ t
     pdf[idx] = lum * rowSin[idx / width];
 }
 
+// The aperture mask's weights (rdh_set_lens): weight[k] = luminance(texel k), texel order, n = width * height texels.
+__global__ __launch_bounds__(256) void k_lens_weights(const float *__restrict__ texels, int n, float *__restrict__ weight) {
+    const int idx = int(blockIdx.x * blockDim.x + threadIdx.x);
+    if (idx >= n) return;
+    weight[idx] = luminance(texel(texels, idx));
+}
+
 // k_light_power for an environment power that never left the device (rdh_scene_set_texture): entries numLights .. n - 1 = *envPower.
 __global__ __launch_bounds__(256) void k_light_power_dev(const LightRec *__restrict__ lights, int numLights, int n,
                                                          const float *__restrict__ envPower, float *__restrict__ power) {

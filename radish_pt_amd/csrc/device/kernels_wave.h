@@ -233,8 +233,10 @@ RD_DEV unsigned subFrameBlocks(const PixelMap &pm, int part, int parts) { return
 // row (looper + b) % 10000, the wrap of State::looper.  trace and shade see path slots only; k_wf_finish folds a pixel's B slots
 // in sample order.
 constexpr int kSobolRows = 10000;  // State::looper wraps here (pathtrace.cu:380-381)
-__global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper, int samples, int part,
-                                                   int parts) {
+// The body is written once for the pinhole kernel and the lens one (k_wf_raygen_lens below; LENS as in kernels_pt.h).
+template <bool LENS>
+RD_DEV void wfRaygen(const DScene &s, const DCamera &cam, const PixelMap &pm, const WaveWorkspace &w, int looper, int samples, int part,
+                     int parts, const DLens &lens) {
     unsigned wg;
     const unsigned nLocal = subFrameBlocks(pm, part, parts);
     const unsigned nGroups = nLocal * (unsigned)samples;
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
     bool listed = false;
     if (valid) {
         Sampler rng = makeSeededRandomEngine(int(((unsigned)looper + b) % (unsigned)kSobolRows), px.index, 0, s.sobol);
-        Ray ray = cameraSample(cam, px.x, px.y, sample4D(rng));
+        Ray ray = cameraSample<LENS>(cam, px.x, px.y, sample4D(rng), lens);
         w.ro[0][p] = make_float4(ray.o.x, ray.o.y, ray.o.z, 0.f);
         w.rd[0][p] = make_float4(ray.d.x, ray.d.y, ray.d.z, 0.f);
         w.accD[p] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -270,6 +272,14 @@ __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelM
     // k_wf_shade marks such rays): no compaction.
     if (inRange) w.rayq[0][p] = valid ? (listed ? -2 - p : p) : -1;
     if (blockIdx.x == 0 && threadIdx.x == 0) w.ctr->rayCount[0].v = int(nGroups) * 64;
+}
+__global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper, int samples, int part,
+                                                   int parts) {
+    wfRaygen<false>(s, cam, pm, w, looper, samples, part, parts, DLens{});
+}
+__global__ __launch_bounds__(256) void k_wf_raygen_lens(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper, int samples,
+                                                        int part, int parts, DLens lens) {
+    wfRaygen<true>(s, cam, pm, w, looper, samples, part, parts, lens);
 }
 
 // ---- trace(k): closest hits of bounce k + shadow rays of bounce k (from shade(k-1)) ---------------------------

@@ -165,8 +165,14 @@ struct SceneState {
     float *envRowSin = nullptr;          // the environment map's row factors, the host's sinf((.5f + i) / height * PI): sent once
     bool envSumValid = false;            // envScratch's sums[0] is the power of the environment map as ds.texData holds it
 
+    // rdh_set_lens (bsdf.h, lensAperture).  Off after every upload and free, like everything here.
+    int lensMode = RDH_LENS_OFF;
+    int lensTex = -1;                    // MASK: the texture whose luminances the table samples
+    AliasRec *lensAlias = nullptr;       // MASK: the alias table over that texture's texels, in texel order
+    void *lensScratch = nullptr;         // the weights + AliasWork laid out for those texels
+
     // rdh_scene_set_geometry (kernels_geometry.h)
-    int primCap = 0;                     // triangles that ds.tris, ds.attrs, ds.primClass, the node allocation, the pairs and prevTris
+    int primCap = 0;                    // triangles that ds.tris, ds.attrs, ds.primClass, the node allocation, the pairs and prevTris
                                          // hold (the upload's count until a larger set arrives; never shrinks)
 };
 
@@ -696,6 +702,24 @@ bool usePackets(uint32_t flags) {
 }
 int packetBudget(uint32_t flags) { return (flags & RDH_PT_WF_SMALL_LISTS) ? 4 : kPacketBudget; }  // tests: packets of 4 visits
 
+// Do this frame's primary rays go through the lens (rdh_set_lens)?  With the lens off or a radius of 0 every entry launches the
+// pinhole instantiations, so such frames are the pinhole's by construction.  lensArgs: what the <.., LENS = true> kernels are handed.
+bool lensActive(const rdh_ctx *c) { return c->scene.haveScene && c->scene.lensMode != RDH_LENS_OFF && c->cam.lensRadius > 0.f; }
+DLens lensArgs(const rdh_ctx *c) {
+    const SceneState &s = c->scene;
+    DLens l{nullptr, s.lensMode, 0, 0};
+    if (s.lensMode == RDH_LENS_MASK) {
+        const int4 info = s.texInfo[(size_t)s.lensTex];
+        l = DLens{s.lensAlias, s.lensMode, info.x, info.y};
+    }
+    return l;
+}
+constexpr const char *kRestirLensText = "rdh_restir_direct: ReSTIR's G-buffer and reprojection are the pinhole's; switch the lens off "
+                                        "(rdh_set_lens) or set lensRadius to 0";
+// Stage 0 of a lens frame as packets (k_wf_trace_primary)?  The packet walk tests every lane's own ray, so either way is correct;
+// which is faster is a measurement.
+constexpr bool kLensPrimaryPackets = true;
+
 // Grid for "4 waves per workgroup, one 8x8 block per wave", padded to a multiple of 8 workgroups (xcdSwizzle).
 unsigned gridFor(const PixelMap &pm) {
     unsigned work = (unsigned)(pm.numBlocks + 3) / 4;
@@ -921,7 +945,7 @@ int wavefrontPrepare(rdh_ctx *c, int maxDepth, uint32_t flags, int parts, WfLaun
     }
     L = WfLaunch{count, sort, walkAll, tree, traceGrid, shadeGrid, parts};
     // stage 0's primary rays as packets, unless told otherwise (the A/B switch within one build); an empty tree keeps k_wf_trace
-    L.primaryBudget = (usePackets(flags) && c->scene.ds.bvhSize > 0) ? packetBudget(flags) : 0;
+    L.primaryBudget = (usePackets(flags) && (kLensPrimaryPackets || !lensActive(c)) && c->scene.ds.bvhSize > 0) ? packetBudget(flags) : 0;
     return RDH_OK;
 }
 
@@ -990,7 +1014,10 @@ int wavefrontPathTrace(rdh_ctx *c, const PixelMap &pm, float *d_direct, float *d
         const unsigned gridBlk = (((nLocal * (unsigned)samples + 3u) / 4u + 7u) / 8u) * 8u;
         L.primaryGroups[h] = nLocal * (unsigned)samples;  // k_wf_raygen's nGroups
         keep(hipMemsetAsync(w.ctr, 0, sizeof(WaveCounters), st), "hipMemsetAsync(wavefront counters)");
-        hipLaunchKernelGGL(k_wf_raygen, dim3(gridBlk), dim3(256), 0, st, c->scene.ds, c->cam, pm, w, looper, samples, h, parts);
+        if (lensActive(c))
+            hipLaunchKernelGGL(k_wf_raygen_lens, dim3(gridBlk), dim3(256), 0, st, c->scene.ds, c->cam, pm, w, looper, samples, h, parts, lensArgs(c));
+        else
+            hipLaunchKernelGGL(k_wf_raygen, dim3(gridBlk), dim3(256), 0, st, c->scene.ds, c->cam, pm, w, looper, samples, h, parts);
     }
     wavefrontStages(c, L, maxDepth, flags, rc);
     for (int h = 0; h < parts && rc == RDH_OK; h++) {
@@ -1463,7 +1490,8 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
         unsigned groups = (((unsigned)(pm.numBlocks + 3) / 4 + 7u) / 8u) * 8u * 4u;  // one wave per workgroup
         const bool pairs = usePairs(c, flags);
         unsigned resGrid = 0;
-        withBools([&](auto pr) { rc = residentGrid(c, k_pt_persistent<false, pr.value>, 64, &resGrid); }, pairs);
+        const bool lens = lensActive(c);
+        withBools([&](auto pr, auto ln) { rc = residentGrid(c, k_pt_persistent<false, pr.value, ln.value>, 64, &resGrid); }, pairs, lens);
         if (rc) return rc;
         const unsigned grid = sharedGrid(c, resGrid, groups);
         const int ovfDepth = c->scene.ds.treeDepth + 1;
@@ -1502,10 +1530,11 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
         c->testOrderBlocks = 0;
         long pp = profBegin(c, flags);
         int2 *const ovf = pairs ? c->treeOvf.as<int2>() : nullptr;
-        withBools([&](auto cnt, auto pr) {
-            hipLaunchKernelGGL((k_pt_persistent<cnt.value, pr.value>), dim3(grid), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper, iter,
-                               maxDepth, d_direct, d_indirect, c->dPersist, order, c->blockCost[cb].as<unsigned>(), ovf, pairs ? ovfDepth : 0);
-        }, count, pairs);
+        withBools([&](auto cnt, auto pr, auto ln) {
+            hipLaunchKernelGGL((k_pt_persistent<cnt.value, pr.value, ln.value>), dim3(grid), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper,
+                               iter, maxDepth, d_direct, d_indirect, c->dPersist, order, c->blockCost[cb].as<unsigned>(), ovf,
+                               pairs ? ovfDepth : 0, lensArgs(c));
+        }, count, pairs, lens);
         profEnd(c, pp);
         // this launch's costs -> running means -> block order for launch n + 2, on the side stream
         HIP_TRY(c, hipEventRecord(c->evFrame, c->stream));
@@ -1517,10 +1546,10 @@ int rdh_path_trace(rdh_ctx *c, float *d_direct, float *d_indirect, int iter, int
     }
     timeBegin(c);
     long pe = profBegin(c, flags);
-    withBools([&](auto cnt) {
-        hipLaunchKernelGGL(k_path_trace_mega<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper,
-                           iter, maxDepth, d_direct, d_indirect);
-    }, count);
+    withBools([&](auto cnt, auto ln) {
+        hipLaunchKernelGGL((k_path_trace_mega<cnt.value, false, ln.value>), dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm,
+                           looper, iter, maxDepth, d_direct, d_indirect, RayDump{}, lensArgs(c));
+    }, count, lensActive(c));
     profEnd(c, pe);
     return timeEnd(c, "pathTrace");
 }
@@ -1632,8 +1661,12 @@ int rdh_path_trace_adaptive(rdh_ctx *c, float *d_direct, float *d_indirect, int3
     hipLaunchKernelGGL(k_ad_scatter, dim3(groups), dim3(256), 0, c->stream, pm, (const int *)d_request, (const int *)a.wgTotals, (int)T, owner);
     keepHip(c, rc, hipMemsetAsync(w.ctr, 0, sizeof(WaveCounters), c->stream), "hipMemsetAsync(wavefront counters)");
     const unsigned genGrid = ((((unsigned)(padded / 64) + 3u) / 4u + 7u) / 8u) * 8u;
-    hipLaunchKernelGGL(k_ad_raygen, dim3(genGrid), dim3(256), 0, c->stream, c->scene.ds, c->cam, pm, w, looper, (const int *)d_count,
-                       (const int *)owner, (int)T);
+    if (lensActive(c))
+        hipLaunchKernelGGL(k_ad_raygen_lens, dim3(genGrid), dim3(256), 0, c->stream, c->scene.ds, c->cam, pm, w, looper, (const int *)d_count,
+                           (const int *)owner, (int)T, lensArgs(c));
+    else
+        hipLaunchKernelGGL(k_ad_raygen, dim3(genGrid), dim3(256), 0, c->stream, c->scene.ds, c->cam, pm, w, looper, (const int *)d_count,
+                           (const int *)owner, (int)T);
     keepHip(c, rc, hipGetLastError(), "k_ad_raygen");
     L.primaryGroups[0] = (unsigned)(padded / 64);  // k_ad_raygen's nGroups
     wavefrontStages(c, L, maxDepth, flags, rc);
@@ -1681,10 +1714,10 @@ int rdh_path_trace_direct(rdh_ctx *c, float *d_direct, int iter, int looper, uin
     HIP_TRY(c, hipSetDevice(c->device));
     PixelMap pm = makePixelMap(c);
     timeBegin(c);
-    withBools([&](auto cnt) {
-        hipLaunchKernelGGL(k_path_trace_direct<cnt.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper,
-                           iter, d_direct);
-    }, (flags & RDH_PT_COUNT) != 0);
+    withBools([&](auto cnt, auto ln) {
+        hipLaunchKernelGGL((k_path_trace_direct<cnt.value, ln.value>), dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm,
+                           looper, iter, d_direct, lensArgs(c));
+    }, (flags & RDH_PT_COUNT) != 0, lensActive(c));
     return timeEnd(c, "pathTraceDirect");
 }
 
@@ -1816,6 +1849,7 @@ int rdh_restir_direct(rdh_ctx *c, float *d_direct, int iter, int looper, const r
                       uint32_t flags) {
     int rc = requireReady(c);
     if (rc) return rc;
+    if (lensActive(c)) return fail(c, RDH_ERR_UNSUPPORTED, kRestirLensText);
     if (!d_direct || !gb || !p || iter < 0 || looper < 0 || looper >= 10000) return fail(c, RDH_ERR_ARGS, "rdh_restir_direct: bad arguments");
     if (!c->resvCur || c->restirPixels != (long long)c->cam.resx * c->cam.resy)
         return fail(c, RDH_ERR_STATE, "rdh_restir_direct before rdh_restir_init (or resolution changed)");
@@ -2263,6 +2297,7 @@ namespace {
 int restirRender(rdh_ctx *c, float *d_directFrame, int iter, int looper, const rdh_gbuffer *gb, const rdh_restir_params *p, uint32_t flags) {
     int rc = requireReady(c);
     if (rc) return rc;
+    if (lensActive(c)) return fail(c, RDH_ERR_UNSUPPORTED, kRestirLensText);
     if (!d_directFrame) return fail(c, RDH_ERR_ARGS, "rdh_restir_direct_gathered: null image");
     if (!c->comm) return fail(c, RDH_ERR_STATE, "no communicator: call rdh_comm_init first");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2557,8 +2592,10 @@ int rdh_dump_rays(rdh_ctx *c, int looper, int maxDepth, float *d_closest, int64_
     hipMemsetAsync(cnt, 0, 16, c->stream);
     hipMemsetAsync(img, 0, px * 6 * sizeof(float), c->stream);
     RayDump d{d_closest, d_any, (long long)capClosest, (long long)capAny, cnt};
-    hipLaunchKernelGGL((k_path_trace_mega<false, true>), dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper, 0,
-                       maxDepth, img, img + px * 3, d);
+    withBools([&](auto ln) {
+        hipLaunchKernelGGL((k_path_trace_mega<false, true, ln.value>), dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm,
+                           looper, 0, maxDepth, img, img + px * 3, d, lensArgs(c));
+    }, lensActive(c));
     unsigned long long h[2] = {0, 0};
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(h, cnt, 16, hipMemcpyDeviceToHost);
@@ -3815,6 +3852,28 @@ int readEnvPower(rdh_ctx *c, float *out) {
     return RDH_OK;
 }
 
+// The aperture mask's table (rdh_set_lens) in two steps, so that a mask no table can be made of is refused before
+// anything it would replace is touched.  lensClassify: n texels -> their luminances and the classified lists in `scratch`, and the
+// weights' sum read back (the one host wait).  lensSweep: those lists -> `table`.
+int lensClassify(rdh_ctx *c, const float *d_texels, int n, void *scratch, const char *what) {
+    const AliasWork w = lightWork(scratch, n);
+    float *weight = static_cast<float *>(scratch);
+    hipLaunchKernelGGL(k_lens_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_texels, n, weight);
+    hipLaunchKernelGGL(k_alias_classify, dim3(1), dim3(64), 0, c->stream, (const float *)weight, n, w);
+    HIP_TRY(c, hipGetLastError());
+    float sum = 0.f;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(&sum, w.sums, sizeof(float), hipMemcpyDeviceToHost));
+    if (!(sum > 0.f && sum <= FLT_MAX))
+        return fail(c, RDH_ERR_ARGS, "%s: the mask's luminances sum to %g: no aperture to sample", what, (double)sum);
+    return RDH_OK;
+}
+int lensSweep(rdh_ctx *c, int n, void *scratch, AliasRec *table) {
+    hipLaunchKernelGGL(k_alias_sweep, dim3(1), dim3(64), 0, c->stream, lightWork(scratch, n), table);
+    HIP_TRY(c, hipGetLastError());
+    return RDH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3836,10 +3895,14 @@ int rdh_scene_set_texture(rdh_ctx *c, int32_t texId, const float *d_texels, int3
     int rc;
     if ((rc = ensureTreeHeader(c))) return rc;
     if (env && ((rc = ensureEnvWork(c)) || (rc = prepareLightRebuild(c)))) return rc;
+    // the aperture mask: classified from the caller's texels first, so a mask without an aperture is refused with the scene as it was
+    const bool mask = s.lensMode == RDH_LENS_MASK && texId == s.lensTex;
+    if (mask && (rc = lensClassify(c, d_texels, info.x * info.y, s.lensScratch, "rdh_scene_set_texture"))) return rc;
 
     if ((rc = waitSideStreams(c))) return rc;  // the texels are rewritten in place
     HIP_TRY(c, hipMemcpyAsync(const_cast<float *>(s.ds.texData) + 3 * (size_t)info.z, d_texels, sizeof(float) * 3 * (size_t)info.x * info.y,
                               hipMemcpyDeviceToDevice, c->stream));
+    if (mask && (rc = lensSweep(c, info.x * info.y, s.lensScratch, s.lensAlias))) return rc;
     if (!env) return RDH_OK;
     enqueueEnvSampler(c, true);
     HIP_TRY(c, hipGetLastError());
@@ -3876,6 +3939,83 @@ long long rdh_debug_read_textures(rdh_ctx *c, int which, void *hostOut, long lon
         const int32_t n[3] = {s.ds.envTex, s.ds.envSamplerLength, s.numTextures};
         memcpy(hostOut, &envPower, 4);
         memcpy(static_cast<char *>(hostOut) + 4, n, 12);
+    }
+    return bytes;
+}
+
+// ---- the lens (bsdf.h, lensAperture) --------------------------------------------------------------------------------------
+int rdh_set_lens(rdh_ctx *c, int mode, int32_t maskTexId) {
+    if (!c) return RDH_ERR_ARGS;
+    SceneState &s = c->scene;
+    if (mode != RDH_LENS_OFF && mode != RDH_LENS_DISK && mode != RDH_LENS_MASK) return fail(c, RDH_ERR_ARGS, "rdh_set_lens: unknown mode %d", mode);
+    if (mode != RDH_LENS_MASK) {  // the table, if there is one, stays with the scene: frames in flight may still read it
+        if (mode == RDH_LENS_DISK && !s.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_set_lens: no scene uploaded");
+        s.lensMode = mode;
+        return RDH_OK;
+    }
+    if (!s.haveScene) return fail(c, RDH_ERR_NO_SCENE, "rdh_set_lens: no scene uploaded");
+    if (maskTexId < 0 || maskTexId >= s.numTextures) return fail(c, RDH_ERR_ARGS, "rdh_set_lens: texture id %d of %d", maskTexId, s.numTextures);
+    const int4 info = s.texInfo[(size_t)maskTexId];
+    const long long texels = (long long)info.x * info.y;
+    if (texels <= 0 || texels > (1ll << 30)) return fail(c, RDH_ERR_ARGS, "rdh_set_lens: texture %d is %dx%d", maskTexId, info.x, info.y);
+    const int n = (int)texels;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensureTreeHeader(c))) return rc;  // (evUpdWait, for waitSideStreams)
+    // a fresh table and scratch: the previous mode and its table stay in force until this mask has proved to have an aperture
+    void *scratch = nullptr;
+    AliasRec *table = nullptr;
+    if ((rc = sceneAlloc(c, &scratch, aliasWorkBytes(n)))) return rc;
+    if ((rc = sceneAlloc(c, &table, sizeof(AliasRec) * (size_t)n)) ||
+        (rc = lensClassify(c, s.ds.texData + 3 * (size_t)info.z, n, scratch, "rdh_set_lens")) || (rc = lensSweep(c, n, scratch, table))) {
+        sceneRelease(c, &table, true);
+        sceneRelease(c, &scratch, true);
+        return rc;
+    }
+    if ((rc = waitSideStreams(c))) return rc;  // sub-frame pipelines in flight read the old table
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    sceneRelease(c, &s.lensAlias, true);
+    sceneRelease(c, &s.lensScratch, true);
+    s.lensAlias = table;
+    s.lensScratch = scratch;
+    s.lensTex = maskTexId;
+    s.lensMode = RDH_LENS_MASK;
+    return RDH_OK;
+}
+
+int rdh_debug_primary_rays(rdh_ctx *c, int looper, float *d_rays6) {
+    int rc = requireReady(c);
+    if (rc) return rc;
+    if (!d_rays6 || looper < 0 || looper >= kSobolRows) return fail(c, RDH_ERR_ARGS, "rdh_debug_primary_rays: bad arguments");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const PixelMap pm = makePixelMap(c);
+    withBools([&](auto ln) {
+        hipLaunchKernelGGL(k_primary_rays<ln.value>, dim3(gridBlocks(pm)), dim3(64), 0, c->stream, c->scene.ds, c->cam, pm, looper, d_rays6,
+                           lensArgs(c));
+    }, lensActive(c));
+    HIP_TRY(c, hipGetLastError());
+    return RDH_OK;
+}
+
+long long rdh_debug_read_lens(rdh_ctx *c, int which, void *hostOut, long long maxBytes) {
+    if (!c) return RDH_ERR_ARGS;
+    const SceneState &s = c->scene;
+    if (!s.haveScene) return fail(c, RDH_ERR_NO_SCENE, "no scene uploaded");
+    const bool mask = s.lensMode == RDH_LENS_MASK;
+    const int4 info = mask ? s.texInfo[(size_t)s.lensTex] : make_int4(0, 0, 0, 0);
+    long long bytes;
+    if (which == 0) bytes = 16;
+    else if (which == 1) bytes = (long long)sizeof(AliasRec) * info.x * info.y;
+    else return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lens: which = %d", which);
+    if (!hostOut) return bytes;
+    if (maxBytes < bytes) return fail(c, RDH_ERR_ARGS, "rdh_debug_read_lens: %lld bytes needed", bytes);
+    if (which == 0) {
+        const int32_t h[4] = {s.lensMode, mask ? s.lensTex : -1, info.x, info.y};
+        memcpy(hostOut, h, 16);
+    } else if (bytes) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(hostOut, s.lensAlias, bytes, hipMemcpyDeviceToHost));
     }
     return bytes;
 }

@@ -16,7 +16,8 @@
 // than one GPU.  (The Python mirror radish_pt_amd/api.py is the host side the other GPU tests and bench.py exercise.)
 //
 // Adaptive sampling (rdh_path_trace_adaptive, rdh_adaptive_plan) has no counterpart here: the reference samples every
-// pixel alike and has no signature to keep.
+// pixel alike and has no signature to keep.  Nor has the lens (rdh_set_lens): the reference's Camera::sample renders a
+// pinhole whatever lensRadius is, and so does everything below.
 //
 // Macros:  RADISH_SHIM_NO_REFERENCE_HEADERS  the including file has already declared glm / Camera / GBuffer / Scene /
 //                                            Settings / State (skip the reference's #includes)

@@ -86,6 +86,7 @@ class SceneData:
         self.sobol = sobol_table()
         # the object table and rest pose of a scene file (load_scene_file; Context.set_objects); procedural scenes have none
         self.objects = self.rest_vertices = self.rest_normals = None
+        self.aperture_mask_tex_id = -1  # a scene file's ApertureMask among `textures` (load_scene_file; Context.set_lens)
 
     def nbytes(self):
         return sum(
@@ -364,5 +365,6 @@ def load_scene_file(path):
     sd = SceneData(os.path.basename(path), p["vertices"], p["normals"], p["texcoords"], p["material_ids"], p["materials"],
                    textures=p["textures"], env_map_tex_id=p["env_map_tex_id"])
     sd.objects, sd.rest_vertices, sd.rest_normals = p["objects"], p["rest_vertices"], p["rest_normals"]
+    sd.aperture_mask_tex_id = p["aperture_mask_tex_id"]  # the file's ApertureMask among sd.textures (-1: Null), for Context.set_lens
     settings = {"trace_depth": p["trace_depth"], "iterations": p["iterations"], "image_name": p["image_name"]}
     return sd, p["camera"], settings
