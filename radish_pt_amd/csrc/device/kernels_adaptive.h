@@ -136,7 +136,7 @@ RD_DEV void adRaygen(const DScene &s, const DCamera &cam, const PixelMap &pm, co
         }
     }
     if (inRange) w.rayq[0][p] = valid ? (listed ? -2 - p : p) : -1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) w.ctr->rayCount[0].v = int(nGroups) * 64;
+    if (blockIdx.x == 0 && threadIdx.x == 0) w.ctr->rayCount[0][0].v = int(nGroups) * 64;
 }
 __global__ __launch_bounds__(256) void k_ad_raygen(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper,
                                                    const int *__restrict__ count, const int *__restrict__ owner, int total) {

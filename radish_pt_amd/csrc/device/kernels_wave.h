@@ -41,15 +41,70 @@ struct alignas(128) WaveCounter {
 #define RD_WF_TICKET_SHARDS 8  // workgroup-ticket counters per stage (workgroupTicket); 1: one chip-wide counter (measurements)
 #endif
 constexpr int kTicketShards = RD_WF_TICKET_SHARDS;
+// The two queues a shade stage appends to, and the head its waves pull packets from, are kept as S shards with a counter each
+// (WfShardMap below): packet j of shade(k) appends to shard j % S and is pulled from head j % S, so a burst of same-address
+// returning atomics is an S-th as long.  1: one counter and one region per queue, the layout until then (measurements).
+// Teapots 1080p, 8 bounces, sorted, one pipeline, S = 1 / 2 / 8: 6.56 / 6.36 / 6.35 ms a frame, eight shards with one head 6.52: the
+// gain is the heads' (profiles/wf_queue_shards/).
+#ifndef RD_WF_QUEUE_SHARDS
+#define RD_WF_QUEUE_SHARDS 8
+#endif
+constexpr int kQueueShards = RD_WF_QUEUE_SHARDS;
+static_assert(kQueueShards >= 1 && kQueueShards <= 16, "RD_WF_QUEUE_SHARDS: 1 .. 16");
+#ifndef RD_WF_HEAD_SHARDS  // heads the pulls are spread over, at most the queues' shards; 1: sharded appends, one head (measurements)
+#define RD_WF_HEAD_SHARDS RD_WF_QUEUE_SHARDS
+#endif
+constexpr int kHeadShards = RD_WF_HEAD_SHARDS;
+static_assert(kHeadShards >= 1 && kHeadShards <= kQueueShards, "RD_WF_HEAD_SHARDS: 1 .. RD_WF_QUEUE_SHARDS");
 struct WaveCounters {
-    WaveCounter rayCount[kMaxWaveDepth + 2];     // rays of bounce k (written by raygen / shade(k-1))
-    WaveCounter shadowCount[kMaxWaveDepth + 2];  // shadow rays emitted by shade(k)
+    WaveCounter rayCount[kMaxWaveDepth + 2][kQueueShards];     // rays of bounce k per shard (raygen: shard 0 / shade(k-1))
+    WaveCounter shadowCount[kMaxWaveDepth + 2][kQueueShards];  // shadow rays emitted by shade(k), per shard
     WaveCounter litCount[kMaxWaveDepth + 2];     // literal-class rays (both kinds) that shade(k-1) set aside for trace(k)
     WaveCounter litShadowCount[kMaxWaveDepth + 2];  // shadow rays that shade(k) put on that list instead of shadowq (rdh_debug_wf_counts)
     WaveCounter traceHead[kMaxWaveDepth + 2];
-    WaveCounter shadeHead[kMaxWaveDepth + 2][4];
+    WaveCounter shadeHead[kMaxWaveDepth + 2][kQueueShards];  // pulls made from head x of shade(k) (wavePull)
     WaveCounter traceTicket[kMaxWaveDepth + 2][kTicketShards];  // workgroupTicket of trace(k) / shade(k)
     WaveCounter shadeTicket[kMaxWaveDepth + 2][kTicketShards];
+    int queueStride[kMaxWaveDepth + 2];  // R of the queues trace(k) / shade(k) read: shard s starts at s * R (stage 0: 0, the identity)
+};
+
+// A sharded queue as its consumers see it.  The producer, shade(k - 1), shades its n records in packets of `packet` records (uniform
+// over the stage); packet j = base / packet belongs to shard j % S and appends at s * R + (what shard s holds so far), with
+// R = ceil(ceil(n / packet) / S) * packet.  A shard receives entries from its own packets only, at most one of a kind per record,
+// so it never outgrows R, and S * R <= n + S * packet: the queues are S * kSortPacket entries longer than the slots (radish_hip.hip).
+// A stage's item space stays dense: item i of a kind lives at s * R + (i - prefix[s]) with prefix[s] <= i < prefix[s + 1], the
+// prefixes being the running sums of the shards' counts.  The counts and the stride are loaded once per kernel with uniform loads
+// and the map is two scalars per shard (first[j], the first item of shard j, and shift[j] = j * R - first[j], kept as its steps)
+// that a lane resolves its item with at hand-out, in S - 1 compares.  Stage 0's queue is shard 0 alone at offset 0 (k_wf_raygen,
+// k_ad_raygen): the identity whatever the stride, which WfSlotWork::find and k_wf_trace_primary read as such.
+RD_DEV int wfQueueStride(int n, int packet) {
+    const int packets = (n + packet - 1) / packet;
+    return ((packets + kQueueShards - 1) / kQueueShards) * packet;
+}
+struct WfShardMap {
+    int first[kQueueShards], step[kQueueShards];  // step[j] = shift[j] - shift[j - 1]: what crossing into shard j adds to the address
+    int total;
+    // `counts`: the S counters of one queue; `itemBase`: where the queue's items start in the stage's item space
+    RD_DEV void load(const WaveCounter *counts, int stride, int itemBase) {
+        int at = 0, shift = 0;
+#pragma unroll
+        for (int j = 0; j < kQueueShards; j++) {
+            first[j] = itemBase + at;
+            step[j] = j * stride - first[j] - shift;
+            shift += step[j];
+            at += __builtin_amdgcn_readfirstlane(counts[j].v);
+        }
+        total = at;
+    }
+    // The queue address of item `i` (of the stage's item space, within this queue's range).  first[] does not decrease, so the
+    // shards at or below the item's own are exactly those with first[j] <= i.  (A sum of steps, not a choice among S shifts: the
+    // compiler makes a table in scratch of the latter.)
+    RD_DEV int at(int i) const {
+        int a = i + step[0];
+#pragma unroll
+        for (int j = 1; j < kQueueShards; j++) a += i >= first[j] ? step[j] : 0;
+        return a;
+    }
 };
 
 // Slots.  A path's HOME slot is its position in bounce 0's identity queue (k_wf_raygen); its two accumulators stay there for the whole
@@ -202,11 +257,20 @@ RD_DEV int workgroupTicket(WaveCounter *tickets) {
 }
 // (wave-uniform, so kept in a scalar register: the VGPR budget of k_wf_trace has no room for it)
 RD_DEV int logicalWave(int wg) { return __builtin_amdgcn_readfirstlane(int(wg * int(blockDim.x >> 6) + int(threadIdx.x >> 6))); }
-// k_wf_shade's pull: the next packet behind the waves' fixed first packets
-RD_DEV int wavePull(int *head, int packet) {
-    int base = 0;
-    if ((threadIdx.x & 63u) == 0u) base = atomicAdd(head, packet);
-    return __shfl(base, 0, 64) + gridWaves() * packet;
+// k_wf_shade's pull: the next packet behind the waves' fixed first packets, for logical wave g of a stage of n records.  Nothing
+// lies behind them if n <= gridWaves * packet: the wave leaves without an atomic (the result is beyond n).  Otherwise wave g pulls
+// from head x = g % Se only, Se = min(S, gridWaves) (S = kHeadShards), and the t-th pull of that head is packet
+// gridWaves + Se * t + x: every head has a wave, so every packet is taken, and a wave whose head has passed n leaves (no stealing:
+// the heads hand out interleaved packets, so they run dry within a packet of each other).
+RD_DEV int wavePull(WaveCounter *heads, int g, int packet, int n) {
+    const int waves = gridWaves();
+    if (n <= waves * packet) return n;
+    const int se = kHeadShards < waves ? kHeadShards : waves, x = g % se;
+    int t = 0;
+    if ((threadIdx.x & 63u) == 0u) t = atomicAdd(&heads[x].v, 1);
+    t = __builtin_amdgcn_readfirstlane(t);
+    // (a pull beyond the last packet is the wave's last: t stays below packets / Se + the waves of the head, far from overflow)
+    return (waves + se * t + x) * packet;
 }
 // k_wf_trace's pull: the next packet behind `headBase`, the end of the stage's fixed first packets (which depends on how many
 // workgroups have list duty, so the caller says where it is).  Called with the whole wave active; the result is wave-uniform.
@@ -271,7 +335,7 @@ RD_DEV void wfRaygen(const DScene &s, const DCamera &cam, const PixelMap &pm, co
     // Bounce 0's queue is the identity over this launch's slots (-1 marks pixels outside the frame; -2 - slot: on the first list, as
     // k_wf_shade marks such rays): no compaction.
     if (inRange) w.rayq[0][p] = valid ? (listed ? -2 - p : p) : -1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) w.ctr->rayCount[0].v = int(nGroups) * 64;
+    if (blockIdx.x == 0 && threadIdx.x == 0) w.ctr->rayCount[0][0].v = int(nGroups) * 64;
 }
 __global__ __launch_bounds__(256) void k_wf_raygen(DScene s, DCamera cam, PixelMap pm, WaveWorkspace w, int looper, int samples, int part,
                                                    int parts) {
@@ -367,8 +431,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PAIRS && !C
     bool stampedDry = false, stampedHeld = false;
     RD_WF_STAMP(0);
 #endif
-    const int nShadow = (k > 0) ? c->shadowCount[k - 1].v : 0;
-    const int nRay = c->rayCount[k].v;
+    // the two queues' shards in the stage's item space (WfShardMap: uniform loads, scalar registers)
+    const int stride = __builtin_amdgcn_readfirstlane(c->queueStride[k]);
+    WfShardMap rayMap, shadowMap;
+#if RD_WF_SHADOW_FIRST
+    shadowMap.load(c->shadowCount[k > 0 ? k - 1 : 0], stride, 0);
+    if (k == 0) shadowMap.total = 0;
+    rayMap.load(c->rayCount[k], stride, shadowMap.total);
+#else
+    rayMap.load(c->rayCount[k], stride, 0);
+    shadowMap.load(c->shadowCount[k > 0 ? k - 1 : 0], stride, rayMap.total);
+    if (k == 0) shadowMap.total = 0;
+#endif
+    const int nShadow = shadowMap.total, nRay = rayMap.total;
     const int total = nShadow + nRay;
     const int *rayq = w.rayq[k & 1];
     const int set = k & 1;  // the state shade(k-1) / raygen wrote (WaveWorkspace)
@@ -495,11 +570,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PAIRS && !C
                     doStart = true;
 #if RD_WF_SHADOW_FIRST
                     isShadow = item < nShadow;
-                    p = isShadow ? w.shadowq[item] : rayq[item - nShadow];
 #else
                     isShadow = item >= nRay;
-                    p = isShadow ? w.shadowq[item - nRay] : rayq[item];
 #endif
+                    p = isShadow ? w.shadowq[shadowMap.at(item)] : rayq[rayMap.at(item)];  // (each map knows where its items start)
                 }
                 resNext += give;
                 taken += give;
@@ -746,6 +820,14 @@ constexpr int kSortPacket = 64 * kSortChunks;    // records a wave bins at a tim
 #ifndef RD_WF_SHADE_WAVES
 #define RD_WF_SHADE_WAVES 1  // waves per SIMD k_wf_shade is held to (1: whatever its 131 VGPRs allow = 3)
 #endif
+// ... and AT MOST, as RD_WF_PAIR_MAX_WAVES holds k_wf_trace's pair variant: the kernel needs 127 to 131 registers, across the step
+// at 128, and which side it lands on moves with unrelated edits (the sharded pull took it to 127).  Four waves per SIMD gained
+// nothing on the tree they were measured on (the entry on the appends; not measured again with the shards) and make
+// every stage's grid, packets and append bursts a third larger: three keep the stage what tests/test_kernel_resources.py pins.  The host
+// holds the resident grid to as many workgroups per CU (radish_hip.hip, wavefrontPrepare).  8: no bound.
+#ifndef RD_WF_SHADE_MAX_WAVES
+#define RD_WF_SHADE_MAX_WAVES 3
+#endif
 // Rays that are not queued ("Rays whose outcome cannot reach the image"; walkAll != 0 — RDH_PT_WALK_ALL, and every
 // counting launch — queues them all, the reference's order of work):
 //   * RD_WF_CULL_LAST: the extension ray shade(maxDepth - 1) emits is walked by trace(maxDepth) only to learn whether it ends on an
@@ -763,8 +845,8 @@ constexpr int kSortPacket = 64 * kSortChunks;    // records a wave bins at a tim
 #ifndef RD_WF_SKIP_NULL_NEE
 #define RD_WF_SKIP_NULL_NEE 1  // 0: queue every shadow ray (measurements)
 #endif
-__global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, WaveWorkspace w, int k, int maxDepth, int sorted,
-                                                                     const float4 *__restrict__ emitBox, int walkAll) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RD_WF_SHADE_WAVES, RD_WF_SHADE_MAX_WAVES)))
+void k_wf_shade(DScene s, WaveWorkspace w, int k, int maxDepth, int sorted, const float4 *__restrict__ emitBox, int walkAll) {
     __shared__ int sSorted[4][kSortPacket];  // per wave of the workgroup: the packet's path slots in class order
     WaveCounters *c = w.ctr;
     // the last bounce's extension rays are tested against the emitter box (uniform loads, this stage only)
@@ -779,8 +861,9 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
     const int lane = int(threadIdx.x & 63u);
     int *mySorted = sSorted[threadIdx.x >> 6];
     {
-        const int q = 0;
-        const int n = c->rayCount[k].v;
+        WfShardMap hitMap;  // this stage's records: the rays trace(k) walked, in item order
+        hitMap.load(c->rayCount[k], __builtin_amdgcn_readfirstlane(c->queueStride[k]), 0);
+        const int n = hitMap.total;
         const int *hitq = w.rayq[k & 1];
         int pendShadows = 0, pendRays = 0;  // entries waiting in the wave's sSorted row for the next append (wave-uniform)
         // unsorted: packets of kShadePacket = 256 records.  sorted: 256 .. kSortPacket = 1 024 records (multiples of 256), as large
@@ -792,10 +875,13 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
             packet = ((perWave + kShadePacket - 1) / kShadePacket) * kShadePacket;
             packet = packet < kShadePacket ? kShadePacket : (packet > kSortPacket ? kSortPacket : packet);
         }
+        // what this stage appends lies in shards of R entries (WfShardMap); trace(k + 1) and shade(k + 1) read R from the counters
+        const int outStride = wfQueueStride(n, packet);
+        if (wg == 0 && threadIdx.x == 0) c->queueStride[k + 1] = outStride;
         int packetEnd = 0;  // sorted: records of the current packet that exist (<= kSortPacket)
         for (int base = logicalWave(wg) * packet, sub = 0, fresh = 1;;) {
             if (sub == packet) {
-                base = wavePull(&c->shadeHead[k][q].v, packet);
+                base = wavePull(c->shadeHead[k], logicalWave(wg), packet, n);
                 sub = 0;
                 fresh = 1;
             }
@@ -807,7 +893,7 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
 #pragma unroll
                 for (int j = 0; j < kSortChunks; j++) {
                     const int i = base + j * 64 + lane;
-                    pp[j] = (j * 64 + lane < packetEnd) ? hitq[i] : -1;
+                    pp[j] = (j * 64 + lane < packetEnd) ? hitq[hitMap.at(i)] : -1;
                     if (pp[j] <= -2) pp[j] = -2 - pp[j];  // a ray trace(k) started first (literal-class list): same path slot
                 }
 #pragma unroll
@@ -839,7 +925,7 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
             // the place in class order inside the packet), unique and below n (WaveWorkspace)
             const int q = base + subNow + lane;
             if (active) {
-                p = sorted ? mySorted[subNow + lane] : hitq[item];
+                p = sorted ? mySorted[subNow + lane] : hitq[hitMap.at(item)];
                 if (p <= -2) p = -2 - p;  // (see the binning above)
                 active = p >= 0;
             }
@@ -889,12 +975,13 @@ __global__ __launch_bounds__(256, RD_WF_SHADE_WAVES) void k_wf_shade(DScene s, W
             pendRays += __popcll(__ballot(emitRay));
             if ((sub & (kAppendSpan - 1)) == 0 || sub == packet || base + sub >= n) {
                 int atS = 0, atR = 0;  // both atomics are in flight together
+                const int shard = (base / packet) % kQueueShards;  // the packet's shard: its counters, its region of either queue
                 if (lane == 0) {
-                    if (pendShadows > 0) atS = atomicAdd(&c->shadowCount[k].v, pendShadows);
-                    if (pendRays > 0) atR = atomicAdd(&c->rayCount[k + 1].v, pendRays);
+                    if (pendShadows > 0) atS = atomicAdd(&c->shadowCount[k][shard].v, pendShadows);
+                    if (pendRays > 0) atR = atomicAdd(&c->rayCount[k + 1][shard].v, pendRays);
                 }
-                atS = __builtin_amdgcn_readfirstlane(atS);
-                atR = __builtin_amdgcn_readfirstlane(atR);
+                atS = __builtin_amdgcn_readfirstlane(atS) + shard * outStride;
+                atR = __builtin_amdgcn_readfirstlane(atR) + shard * outStride;
                 int *nextq = w.rayq[(k + 1) & 1];
                 for (int o = subNow & ~(kAppendSpan - 1); o < sub; o += 64) {  // the chunks shaded since the last append
                     const int f = mySorted[o + lane], qq = base + o + lane;

@@ -841,9 +841,11 @@ int wavefrontEnsureSlots(rdh_ctx *c, long long slots) {  // workspace 0: the who
                 (rc = wfAlloc(c, &w.rng[set], n)))
                 return rc;
         }
+        // the queues lie in kQueueShards regions of R entries, S * R <= n + S * packet (kernels_wave.h, WfShardMap)
+        const size_t nq = n + (size_t)kQueueShards * (size_t)kSortPacket;
         if ((rc = wfAlloc(c, &w.accD, n)) || (rc = wfAlloc(c, &w.accI, n)) ||
-            (rc = wfAlloc(c, &w.hit, n)) || (rc = wfAlloc(c, &w.rayq[0], n)) || (rc = wfAlloc(c, &w.rayq[1], n)) ||
-            (rc = wfAlloc(c, &w.shadowq, n)) || (rc = wfAlloc(c, &w.ctr, 1)) || (rc = wfAlloc(c, &w.litq[0], (size_t)kWfLitCap)) ||
+            (rc = wfAlloc(c, &w.hit, n)) || (rc = wfAlloc(c, &w.rayq[0], nq)) || (rc = wfAlloc(c, &w.rayq[1], nq)) ||
+            (rc = wfAlloc(c, &w.shadowq, nq)) || (rc = wfAlloc(c, &w.ctr, 1)) || (rc = wfAlloc(c, &w.litq[0], (size_t)kWfLitCap)) ||
             (rc = wfAlloc(c, &w.litq[1], (size_t)kWfLitCap)))
             return rc;
         w.litCap = 0;
@@ -892,6 +894,11 @@ int wavefrontPrepare(rdh_ctx *c, int maxDepth, uint32_t flags, int parts, WfLaun
         int cus = 0;
         if (int rc = cuCount(c, &cus)) return rc;
         traceRes = std::min(traceRes, (unsigned)cus * (unsigned)RD_WF_PAIR_MAX_WAVES);
+    }
+    if (RD_WF_SHADE_MAX_WAVES < 8) {  // likewise k_wf_shade (kernels_wave.h, RD_WF_SHADE_MAX_WAVES)
+        int cus = 0;
+        if (int rc = cuCount(c, &cus)) return rc;
+        shadeRes = std::min(shadeRes, (unsigned)cus * (unsigned)RD_WF_SHADE_MAX_WAVES);
     }
     // persistent grids: the whole resident grid for every sub-frame pipeline (two pipelines serialised on one hardware queue
     // then each run at full width; pipelines on different queues share the chip through the dispatcher), divided only between
@@ -2739,16 +2746,20 @@ int rdh_debug_wf_counts(rdh_ctx *c, int32_t *rays, int32_t *shadows, int32_t cap
     if (c->wfLastStages <= 0 || capacity < c->wfLastStages) return RDH_OK;
     std::fill(rays, rays + c->wfLastStages, 0);
     std::fill(shadows, shadows + c->wfLastStages, 0);
-    std::vector<WaveCounter> host(3 * (size_t)c->wfLastStages);
-    const size_t bytes = sizeof(WaveCounter) * (size_t)c->wfLastStages;
+    // a queue's count is the sum over its shards (kernels_wave.h, WfShardMap): [stage][shard] rows, copied whole
+    const size_t rows = (size_t)c->wfLastStages, sharded = rows * (size_t)kQueueShards;
+    std::vector<WaveCounter> host(2 * sharded + rows);
     for (int h = 0; h < c->wfLastParts; h++) {
         const WaveCounters *d = c->wf[h].ctr;
-        HIP_TRY(c, hipMemcpy(host.data(), d->rayCount, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(host.data() + c->wfLastStages, d->shadowCount, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(host.data() + 2 * c->wfLastStages, d->litShadowCount, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(host.data(), d->rayCount, sizeof(WaveCounter) * sharded, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(host.data() + sharded, d->shadowCount, sizeof(WaveCounter) * sharded, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(host.data() + 2 * sharded, d->litShadowCount, sizeof(WaveCounter) * rows, hipMemcpyDeviceToHost));
         for (int k = 0; k < c->wfLastStages; k++) {
-            rays[k] += host[k].v;
-            shadows[k] += host[c->wfLastStages + k].v + host[2 * c->wfLastStages + k].v;
+            for (int s = 0; s < kQueueShards; s++) {
+                rays[k] += host[(size_t)k * kQueueShards + s].v;
+                shadows[k] += host[sharded + (size_t)k * kQueueShards + s].v;
+            }
+            shadows[k] += host[2 * sharded + k].v;
         }
     }
     return RDH_OK;
